@@ -75,7 +75,14 @@ def parse():
     p.add_argument("--data-c5", default="philox", choices=["philox", "pcg64"],
                    help="c5 inputs: philox = BASELINE.md §4's distributions from torch's device generator (seconds); "
                         "pcg64 = its frozen numpy stream (generated on one host core: ~1 min for 10^8 rows)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64 / "
+                        "float32): a fixed, seeded sample of rows of every output, values and validity; the sub-workloads "
+                        "of the default line as DIR/<workload>_<name>.npy.  Rank 0's shard only.  At most 64 MB in all")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def effective_cores():
@@ -421,6 +428,115 @@ def verify_outputs(workload, rows, dbatch, result):
                        "every output, values and validity, bit for bit"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240607
+
+
+def dump_sample(n, k):
+    """The rows of an n-row output that --dump-outputs writes: all of them up to k, else a fixed, seeded sample of
+    about k (sorted, distinct; the same for the same n on every run and every build)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.Generator(np.random.PCG64(DUMP_SEED + n)).integers(0, n, k, dtype=np.int64))
+
+
+def dump_arrays(wl):
+    """What the last timed step left for a caller, as {name: float64 / float32 numpy array} of sampled rows.  Fixed-
+    width values become float64 (exact for the integers here; decimal128 as four 32-bit limbs, low first), validity
+    and boolean bits float32 0/1, strings their byte lengths and bytes (zero-padded rows); a value under a null is 0."""
+    import numpy as np
+    import pyarrow as pa
+    import torch
+    out = {}
+
+    def rows_of(n, k, device):
+        r = dump_sample(n, k)
+        return r, torch.from_numpy(r).to(device)
+
+    def bits(buf, idx):
+        return ((buf[idx >> 3].to(torch.int64) >> (idx & 7)) & 1)
+
+    def valid(col, idx):
+        return torch.ones_like(idx) if col.validity is None else bits(col.validity, idx)
+
+    def fixed(col, idx, dtype):
+        return col.data.view(dtype)[idx].to(torch.float64)
+
+    def put(name, t, valid=None, dtype=np.float64):
+        if valid is not None:
+            t = torch.where(valid.bool().view(-1, *([1] * (t.dim() - 1))), t, torch.zeros_like(t))
+        out[name] = t.cpu().numpy().astype(dtype)
+
+    k = (1 << 18) if wl.name == "c2" else (1 << 16)
+    if wl.name in ("c1", "c2", "c4"):
+        rows, idx = rows_of(wl.rows, k, wl.outs[0].data.device)
+        out["rows"] = rows.astype(np.float64)
+        names = {"c1": ["e0"], "c2": [f"e{e}" for e in range(10)], "c4": ["disc_price", "charge", "days"]}[wl.name]
+        for name, o in zip(names, wl.outs):
+            v = valid(o, idx)
+            if pa.types.is_decimal(o.type):
+                w = o.data.view(torch.int64)[:2 * wl.rows].view(-1, 2)[idx]
+                limbs = torch.stack([w[:, 0] & 0xffffffff, (w[:, 0] >> 32) & 0xffffffff,
+                                     w[:, 1] & 0xffffffff, (w[:, 1] >> 32) & 0xffffffff], 1).to(torch.float64)
+                put(name, limbs, v)
+            else:
+                dt = torch.float64 if pa.types.is_floating(o.type) else {32: torch.int32, 64: torch.int64}[o.type.bit_width]
+                put(name, fixed(o, idx, dt), v)
+            put(name + "_valid", v, dtype=np.float32)
+    elif wl.name == "c5":
+        like, sub, up = wl.result()
+        rows, idx = rows_of(wl.rows, k, like.data.device)
+        out["rows"] = rows.astype(np.float64)
+        put("like", bits(like.data, idx), valid(like, idx), np.float32)
+        put("like_valid", valid(like, idx), dtype=np.float32)
+        for name, o in (("substr", sub), ("upper", up)):
+            v = valid(o, idx)
+            offs = o.offsets.view(torch.int32).to(torch.int64)
+            start, lens = offs[idx], offs[idx + 1] - offs[idx]
+            width = max(1, min(256, int(lens.max()) if lens.numel() else 1))
+            col = torch.arange(width, device=idx.device).view(1, -1)
+            pos, inside = start.view(-1, 1) + col, col < lens.view(-1, 1)
+            byts = torch.where(inside, o.data[torch.clamp(pos, max=o.data.numel() - 1)].to(torch.int64), 0)
+            put(name + "_len", lens.to(torch.float64), v, np.float32)
+            put(name + "_bytes", byts.to(torch.float64), v, np.float32)
+            put(name + "_valid", v, dtype=np.float32)
+    elif wl.name == "c3":
+        sel = wl.last
+        n = sel.num_slots                        # (reads the device-resident count of the last step)
+        pos_np, pos = rows_of(n, k, sel.indices.device)
+        out["num_slots"] = np.array([n], dtype=np.float64)
+        out["positions"] = pos_np.astype(np.float64)
+        put("indices", sel.indices.view(torch.int32)[pos].to(torch.int64) & 0xffffffff)
+    elif wl.name == "k2f":
+        outs, sel = wl.last
+        n = sel.num_slots
+        pos_np, pos = rows_of(n, k, sel.indices.device)
+        out["num_slots"] = np.array([n], dtype=np.float64)
+        out["positions"] = pos_np.astype(np.float64)
+        put("indices", sel.indices.view(torch.int32)[pos].to(torch.int64) & 0xffffffff)
+        v = valid(outs[0], pos)
+        put("a_plus_b", fixed(outs[0], pos, torch.int64), v)
+        put("a_plus_b_valid", v, dtype=np.float32)
+    else:
+        raise KeyError(wl.name)
+    return out
+
+
+def dump_outputs(wl, directory, prefix="", budget=None):
+    """Write dump_arrays(wl) as directory/<prefix><name>.npy; returns the bytes written.  Refuses (before writing
+    anything) what would take the directory past DUMP_LIMIT_BYTES (budget = what is left of it)."""
+    import numpy as np
+    arrays = dump_arrays(wl)
+    size = sum(a.nbytes for a in arrays.values())
+    left = DUMP_LIMIT_BYTES if budget is None else budget
+    if size > left:
+        raise RuntimeError(f"--dump-outputs: {wl.name}'s sample takes {size} bytes, {left} are left of the 64 MB")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{prefix}{name}.npy"), a)
+    return size
+
 
 def hbm_ceilings(bytes_per_buffer=4 << 30):
     """Read-only / write-only / copy rate of plain streaming kernels on THIS box, in THIS process
@@ -495,6 +611,7 @@ def main_inproc(args):
     bar = threading.Barrier(n)
     elapsed = [0.0] * n
     errors = []
+    kept = {}
 
     def work(r):
         try:
@@ -513,6 +630,8 @@ def main_inproc(args):
                 torch.cuda.synchronize()
                 bar.wait()
                 elapsed[r] = time.perf_counter() - t0
+                if r == 0 and args.dump_outputs:
+                    kept["outs"] = outs
         except Exception as e:
             errors.append((r, repr(e)))
             try:
@@ -526,6 +645,9 @@ def main_inproc(args):
         t.join()
     if errors:
         raise SystemExit(f"in-process bench failed: {errors}")
+    if args.dump_outputs:
+        import types
+        dump_outputs(types.SimpleNamespace(name="c2", rows=rows, outs=kept["outs"]), args.dump_outputs)
     el = max(elapsed)
     total_rows = rows * n
     print(json.dumps({
@@ -694,7 +816,7 @@ def setup_workload(name, rows, args, rank=0):
         def step():
             # (asynchronous, like the other workloads' steps: the slot count stays in device memory, where a selection-mode
             # Projector reads it — no host wait between steps, so a host thread that loses its core does not idle the GPU)
-            wl.obj.evaluate_device(wl.dbatch, "int32", out=wl.out, sync=False)
+            wl.last = wl.obj.evaluate_device(wl.dbatch, "int32", out=wl.out, sync=False)
 
         def result():
             wl.out.fill_(-1)       # the indices the check reads are written by THIS call, after the loop's
@@ -706,7 +828,7 @@ def setup_workload(name, rows, args, rank=0):
         wl.bytes_per_row, wl.read_per_row = 16 + (4 + 8 + 1 / 8) * share, 16
 
         def step():
-            wl.obj.evaluate_device(wl.dbatch, outputs=wl.outs, indices=wl.out, sync=False)
+            wl.last = wl.obj.evaluate_device(wl.dbatch, outputs=wl.outs, indices=wl.out, sync=False)
 
         def result():
             wl.out.fill_(-1)
@@ -986,6 +1108,8 @@ def sub_line(name, args):
     placement = pool_outputs(wl, min(args.pool_candidates, args.sub_placements))
     trials = search_placements(wl, min(args.placements, args.sub_placements))
     elapsed, dev_ms, prewarm = timed_loop(wl, args.sub_steps, args.sub_warmup, prewarm_s=0.25)
+    if args.dump_outputs:
+        args.dump_left -= dump_outputs(wl, args.dump_outputs, prefix=name + "_", budget=args.dump_left)
     verification = verify(wl, args.no_verify)
     roof, achieved, mean_ms = roofline_of(wl, dev_ms, trials, True, placement)
     metric, dtype, text = WORKLOAD_TEXT[name]
@@ -1083,6 +1207,9 @@ def main():
     if sampler is not None and sampler.dev is None:
         sampler = BoxSampler(None)   # bus id did not match a sysfs path: take the first amdgpu card
     elapsed, dev_ms, prewarm = timed_loop(wl, args.steps, args.warmup, barrier=barrier, sampler=sampler)
+    # what the last timed step computed, before anything else touches the outputs (rank 0's shard)
+    if args.dump_outputs and rank == 0:
+        args.dump_left = DUMP_LIMIT_BYTES - dump_outputs(wl, args.dump_outputs)
 
     # what did the timed loop leave behind?  (outside the timed region; every rank checks its own shard)
     verification = verify(wl, args.no_verify)
@@ -1205,6 +1332,9 @@ def main():
                 verification = {"ok": False, "what": "a sub-workload failed: " + ", ".join(
                     k for k, v in subs.items() if not v.get("verified"))}
                 line["verified"] = False
+        if args.dump_outputs:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": DUMP_LIMIT_BYTES - args.dump_left,
+                                      "of": "the last timed step of every workload in this line (a seeded sample of rows)"}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -32,3 +32,43 @@ def test_short_cpu_baselines_run_on_bounded_samples():
         b = bench.short_cpu_baseline(name, 0.2)
         assert b["kind"] == "port" and b["unit"] == "million rows/s" and b["value"] > 0 and b["cores"] >= 1, (name, b)
         assert "passes x" in b["sample"]
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_what_the_last_step_left(tmp_path, monkeypatch):
+    """--dump-outputs DIR: DIR/<name>.npy in float64 / float32, the same sampled rows on every run, values under a null
+    written as 0, at most 64 MB (here: C2's ten outputs and C3's selection vector in host tensors, no device)."""
+    import types
+    import numpy as np
+    import pyarrow as pa
+    import pytest
+    import torch
+    from gandiva_amd.gandiva import DeviceColumn, SelectionVector
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path)])
+    assert bench.parse().dump_outputs == str(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    n = 1 << 20
+    rng = np.random.default_rng(5)
+    valid = rng.random(n) >= 0.1
+    vals = [rng.standard_normal(n) for _ in range(10)]
+    outs = [DeviceColumn(pa.float64(), n, torch.from_numpy(np.packbits(valid, bitorder="little")),
+                         torch.from_numpy(v).view(torch.uint8)) for v in vals]
+    size = bench.dump_outputs(types.SimpleNamespace(name="c2", rows=n, outs=outs), str(tmp_path))
+    assert 0 < size <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, bench.dump_sample(n, 1 << 18))
+    r = rows.astype(np.int64)
+    for e in range(10):
+        got, ok = np.load(tmp_path / f"e{e}.npy"), np.load(tmp_path / f"e{e}_valid.npy")
+        assert got.dtype == np.float64 and ok.dtype == np.float32
+        assert np.array_equal(ok, valid[r]) and np.array_equal(got, np.where(valid[r], vals[e][r], 0.0))
+    idx = np.flatnonzero(valid).astype(np.uint32)
+    buf = torch.from_numpy(np.concatenate([idx, np.zeros(n - idx.size, np.uint32)]).view(np.int32))
+    sel = SelectionVector(2, buf, None, device=True, count_tensor=torch.tensor([idx.size]))
+    got = bench.dump_arrays(types.SimpleNamespace(name="c3", rows=n, last=sel))
+    assert got["num_slots"][0] == idx.size
+    assert np.array_equal(got["indices"], idx[got["positions"].astype(np.int64)].astype(np.float64))
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(types.SimpleNamespace(name="c3", rows=n, last=sel), str(tmp_path / "small"), budget=1024)

@@ -6,7 +6,8 @@ path (C ABI), and the rank-ordered concatenation must equal the unsharded oracle
   * C3 filter: local indices + row_base rebasing + the count exchange (gloo all_gather);
   * C5 var-len: per-shard offsets rebased on concatenation (shard.concat_varlen_device).
 
-There is one GPU on the test box, so the ranks are processes sharing cuda:0 over gloo — the
+There is one GPU on the test box, so the ranks are processes sharing cuda:0: their device work runs
+at most MAX_GPU_RANKS processes at a time, then all N ranks exchange the counts over gloo — the
 same rendezvous, barrier and exchange code the driver's multi-GPU run uses with nccl."""
 import os
 import socket
@@ -29,61 +30,91 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, n, tmpdir):
+# Rank processes that hold the GPU at the same time, next to the test process itself (the 8-rank case runs its ranks'
+# device work in two waves: every process that opens the shared GPU adds a context on it).
+MAX_GPU_RANKS = 4
+
+
+def _gpu_worker(rank, world, n, tmpdir):
+    """Rank `rank`'s device work, in a process of its own: its row range of the logical HBM-resident batch through the
+    HIP path (C ABI).  No collective here: the count exchange runs in _exchange_worker."""
     import torch
-    import torch.distributed as dist
     import gandiva_amd as gandiva
+    torch.cuda.set_device(0)
+    # ---- C2: every rank holds the logical batch in HBM and evaluates only its row range
+    d2 = gandiva.DeviceBatch.from_arrow(W.c2_batch(n))
+    mine, _ = shard.shard_device_batch(d2, world, rank)
+    exprs = W.c2_expressions()
+    if mine.num_rows:
+        outs = gandiva.make_projector(W.c2_schema(), exprs, None).evaluate_device(mine)
+        torch.cuda.synchronize()
+        arrays = [o.to_arrow() for o in outs]
+        with pa.ipc.new_file(os.path.join(tmpdir, f"c2_{rank}.arrow"),
+                             pa.schema([(f"e{i}", pa.float64()) for i in range(len(arrays))])) as w:
+            w.write_batch(pa.RecordBatch.from_arrays(arrays, names=[f"e{i}" for i in range(len(arrays))]))
+    # ---- C3: local selection + base (the counts are exchanged on the host, by _exchange_worker)
+    d3 = gandiva.DeviceBatch.from_arrow(W.c3_batch(n, 0.1))
+    m3, base = shard.shard_device_batch(d3, world, rank)
+    if m3.num_rows:
+        sel = gandiva.make_filter(W.c3_schema(), W.c3_condition()).evaluate_device(m3, "int32")
+        idx = sel.indices[:sel.num_slots].cpu().numpy().view(np.uint32)
+    else:
+        idx = np.zeros(0, np.uint32)
+    np.save(os.path.join(tmpdir, f"c3_local{rank}.npy"), idx)
+    np.save(os.path.join(tmpdir, f"c3_base{rank}.npy"), np.array([base], dtype=np.int64))
+    # ---- C5: var-len outputs per shard (offsets local to the shard)
+    d5 = gandiva.DeviceBatch.from_arrow(W.c5_batch(n, 0.1))
+    m5, _ = shard.shard_device_batch(d5, world, rank)
+    if m5.num_rows:
+        outs = gandiva.make_projector(W.c5_schema(), W.c5_expressions(), None).evaluate_device(m5)
+        torch.cuda.synchronize()
+        arrays = [o.to_arrow() for o in outs]
+        with pa.ipc.new_file(os.path.join(tmpdir, f"c5_{rank}.arrow"),
+                             pa.schema([("like", pa.bool_()), ("sub", pa.string()), ("up", pa.string())])) as w:
+            w.write_batch(pa.RecordBatch.from_arrays(arrays, names=["like", "sub", "up"]))
+        if rank == 0 and world > 1:
+            # the device-side join of two shards' var-len outputs, checked against pyarrow's
+            torch.save({"off": outs[2].offsets.cpu(), "dat": outs[2].data[:outs[2].data_used].cpu(),
+                        "n": outs[2].length}, os.path.join(tmpdir, "c5_up0.pt"))
+
+
+def _exchange_worker(rank, world, port, tmpdir):
+    """All `world` ranks at once over gloo: the count exchange and rebasing of C3's local selections (host only)."""
+    import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        torch.cuda.set_device(0)
-        # ---- C2: every rank holds the logical batch in HBM and evaluates only its row range
-        d2 = gandiva.DeviceBatch.from_arrow(W.c2_batch(n))
-        mine, _ = shard.shard_device_batch(d2, world, rank)
-        exprs = W.c2_expressions()
-        if mine.num_rows:
-            outs = gandiva.make_projector(W.c2_schema(), exprs, None).evaluate_device(mine)
-            torch.cuda.synchronize()
-            arrays = [o.to_arrow() for o in outs]
-            with pa.ipc.new_file(os.path.join(tmpdir, f"c2_{rank}.arrow"),
-                                 pa.schema([(f"e{i}", pa.float64()) for i in range(len(arrays))])) as w:
-                w.write_batch(pa.RecordBatch.from_arrays(arrays, names=[f"e{i}" for i in range(len(arrays))]))
-        # ---- C3: local selection + base, counts exchanged on the host
-        d3 = gandiva.DeviceBatch.from_arrow(W.c3_batch(n, 0.1))
-        m3, base = shard.shard_device_batch(d3, world, rank)
-        if m3.num_rows:
-            sel = gandiva.make_filter(W.c3_schema(), W.c3_condition()).evaluate_device(m3, "int32")
-            idx = sel.indices[:sel.num_slots].cpu().numpy().view(np.uint32)
-        else:
-            idx = np.zeros(0, np.uint32)
+        idx = np.load(os.path.join(tmpdir, f"c3_local{rank}.npy"))
+        base = int(np.load(os.path.join(tmpdir, f"c3_base{rank}.npy"))[0])
         counts = shard.exchange_counts(len(idx))
         np.save(os.path.join(tmpdir, f"c3_idx{rank}.npy"), shard.rebase_indices(idx, base))
         np.save(os.path.join(tmpdir, f"c3_off{rank}.npy"), shard.global_offsets(counts))
-        # ---- C5: var-len outputs per shard (offsets local to the shard)
-        d5 = gandiva.DeviceBatch.from_arrow(W.c5_batch(n, 0.1))
-        m5, _ = shard.shard_device_batch(d5, world, rank)
-        if m5.num_rows:
-            outs = gandiva.make_projector(W.c5_schema(), W.c5_expressions(), None).evaluate_device(m5)
-            torch.cuda.synchronize()
-            arrays = [o.to_arrow() for o in outs]
-            with pa.ipc.new_file(os.path.join(tmpdir, f"c5_{rank}.arrow"),
-                                 pa.schema([("like", pa.bool_()), ("sub", pa.string()), ("up", pa.string())])) as w:
-                w.write_batch(pa.RecordBatch.from_arrays(arrays, names=["like", "sub", "up"]))
-            if rank == 0 and world > 1:
-                # the device-side join of two shards' var-len outputs, checked against pyarrow's
-                torch.save({"off": outs[2].offsets.cpu(), "dat": outs[2].data[:outs[2].data_used].cpu(),
-                            "n": outs[2].length}, os.path.join(tmpdir, "c5_up0.pt"))
         dist.barrier()
     finally:
         dist.destroy_process_group()
+
+
+def _run_gpu_ranks(world, n, tmpdir):
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    for first in range(0, world, MAX_GPU_RANKS):
+        procs = [ctx.Process(target=_gpu_worker, args=(r, world, n, tmpdir))
+                 for r in range(first, min(world, first + MAX_GPU_RANKS))]
+        for p in procs:
+            p.start()
+        for p in procs:
+            p.join()
+        failed = [(r, p.exitcode) for r, p in zip(range(first, world), procs) if p.exitcode != 0]
+        assert not failed, f"rank processes failed (rank, exit code): {failed}"
 
 
 @pytest.mark.parametrize("world,n", [(2, 70001), (8, 200_003)])
 def test_row_sharded_hip_evaluation_matches_unsharded_oracle(world, n, tmp_path):
     import torch.multiprocessing as mp
     from oracle import oracle
-    mp.spawn(_worker, args=(world, _free_port(), n, str(tmp_path)), nprocs=world, join=True)
+    _run_gpu_ranks(world, n, str(tmp_path))
+    mp.spawn(_exchange_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     ranks = [r for r in range(world) if shard.shard_bounds(n, world, r)[1] > shard.shard_bounds(n, world, r)[0]]
     # C2: rank-ordered concatenation == unsharded evaluation
     exprs = W.c2_expressions()
