@@ -3055,6 +3055,230 @@ GDV_DEV bool gdv_range_any(const gdv_uint64* bm, gdv_int32 lo, gdv_int32 hi) {
   return any;
 }
 
+// ------------------------------------------------------------------ string tail: split_part, substring_index, repeat, space,
+// translate.  split_part / substring_index return narrower views of their text (any consumer takes them, as it takes
+// substr's); repeat / space are GDV_MAP_CYCLE values (the cyclic view lpad / rpad materialise); translate is a value of its
+// own kind, GDV_MAP_TRANSLATE, which is NOT one of GDV_MAP_SPECIAL: only plans that hold a translate() copy their outputs
+// through the *_ext entry points below, so every other plan's copy code stays what it was.
+//
+// The delimiter is searched for bytewise, left to right, without overlap, in the text read through its case map.  A
+// delimiter without a case map of its own whose bytes — and the text's — are readable with raw 8-byte loads (literals in the
+// constant block, column rows flagged GDV_STR_INBUF) takes the word-at-a-time search; anything else compares byte by byte.
+GDV_DEV gdv_int32 gdv_find_delim(const gdv_str& s, gdv_int32 from, const gdv_str& d) {
+  const gdv_int32 cm = s.map & GDV_MAP_CASE, dm = d.map & GDV_MAP_CASE;
+  if ((s.flags & d.flags & GDV_STR_INBUF) && dm == 0) return gdv_find_raw(s.p, s.len, cm, from, d.p, d.len);
+  for (gdv_int32 i = from; i + d.len <= s.len; i++)
+    if (gdv_match_row(s.p, i, s.len, cm, d.p, d.len, dm)) return i;
+  return -1;
+}
+// split_part(text, delimiter, index): field `index` (1-based) of text split on the delimiter.  index < 1 is an execution
+// error; an empty text or delimiter gives the text; an index past the last field gives "".
+GDV_DEV gdv_str split_part_utf8_utf8_int32(gdv_ctx ctx, gdv_str s, const gdv_str& d, gdv_int32 index) {
+  if (index < 1) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    s.len = 0;
+    return s;
+  }
+  if (s.len <= 0 || d.len <= 0) return s;
+  for (gdv_int32 k = 1, start = 0;; k++) {
+    const gdv_int32 at = gdv_find_delim(s, start, d);
+    if (k == index) {
+      const gdv_int32 end = at < 0 ? s.len : at;
+      s.p += start;
+      s.len = end - start;
+      return s;
+    }
+    if (at < 0) {
+      s.len = 0;
+      return s;
+    }
+    start = at + d.len;
+  }
+}
+// substring_index(text, delimiter, count): with n occurrences of the delimiter, count > 0: the bytes before occurrence
+// `count` (the text when count > n); count < 0: the bytes after occurrence n - |count| + 1 (the text when |count| > n);
+// count 0, an empty text or an empty delimiter: "".  Raises nothing (the context is the signature's).
+GDV_DEV gdv_str substring_index_utf8_utf8_int32(gdv_ctx ctx, gdv_str s, const gdv_str& d, gdv_int32 count) {
+  (void)ctx;
+  if (count == 0 || s.len <= 0 || d.len <= 0) {
+    s.len = 0;
+    return s;
+  }
+  gdv_int64 want = count;
+  if (count < 0) {  // occurrence n - |count| + 1 from the left: n first
+    gdv_int64 n = 0;
+    for (gdv_int32 at = gdv_find_delim(s, 0, d); at >= 0; at = gdv_find_delim(s, at + d.len, d)) n++;
+    want = n + (gdv_int64)count + 1;
+    if (want < 1) return s;
+  }
+  gdv_int32 at = -d.len;
+  for (gdv_int64 k = 0; k < want; k++) {
+    at = gdv_find_delim(s, at + d.len, d);
+    if (at < 0) return s;  // (count > n)
+  }
+  if (count > 0) {
+    s.len = at;
+  } else {
+    s.p += at + d.len;
+    s.len -= at + d.len;
+  }
+  return s;
+}
+// repeat(text, n): the text n times — a cyclic view of it.  n < 0 is an execution error (an empty text gives "" first);
+// results above INT32_MAX bytes are an execution error (larger batch totals are refused by the host, as for any output).
+GDV_DEV gdv_str repeat_utf8_int32(gdv_ctx ctx, gdv_str s, gdv_int32 n) {
+  gdv_str r = gdv_empty_str();
+  if (n == 0 || s.len <= 0) return r;
+  const gdv_int64 total = (gdv_int64)s.len * n;
+  if (n < 0 || total > 0x7fffffffll) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return r;
+  }
+  r = s;
+  r.flags &= ~GDV_STR_LEAD;
+  r.lead = (gdv_uint64)s.len;
+  r.len = (gdv_int32)total;
+  r.map = (s.map & GDV_MAP_CASE) | GDV_MAP_CYCLE;
+  return r;
+}
+// space(n): n spaces — a one-byte literal read cyclically.  n <= 0 gives ""; above INT32_MAX bytes: execution error.
+GDV_DEV gdv_str space_int64(gdv_ctx ctx, gdv_int64 n) {
+  gdv_str r = gdv_empty_str();
+  if (n <= 0) return r;
+  if (n > 0x7fffffffll) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return r;
+  }
+  r.p = (const gdv_uint8*)" ";
+  r.lim = r.p + 1;
+  r.flags = GDV_STR_ASCII;  // (no INBUF: the cyclic copy reads byte by byte)
+  r.lead = 1;
+  r.len = (gdv_int32)n;
+  r.map = GDV_MAP_CYCLE;
+  return r;
+}
+GDV_DEV gdv_str space_int32(gdv_ctx ctx, gdv_int32 n) { return space_int64(ctx, (gdv_int64)n); }
+
+// translate(text, from, to) with literal from / to.  The planner lays out the table once per expression in the constant
+// block: int32 kind, int32 count, 8 unused bytes, then
+//   kind 0 (from and to both ASCII): 256 bytes, entry c = the byte ASCII character c becomes, GDV_TR_DELETE to drop it
+//          (entries >= 0x80 are never read: continuation and lead bytes cannot match an ASCII character);
+//   kind 1 (otherwise): `count` entries of four uint32 — key (the character's bytes, packed little-endian: one-to-one with
+//          its code point), replacement length (0: deleted), replacement offset from the table start, unused — then the
+//          replacement bytes.  First occurrence in `from` wins; the planner keeps only that one.
+// The row function walks the characters, raises on text that is not UTF-8 (a byte that cannot lead a character, a
+// character cut by the end of the text, a continuation byte that is not 10xxxxxx) and returns the result's length; the
+// copy (gdv_copy_translated) only writes.  The value: p = the text, lead = its length, lead_p = the table.
+#define GDV_MAP_TRANSLATE 8192
+#define GDV_TR_DELETE 0xFF
+// bytes of the well-formed character at byte i of p (length len), 0 when it is not one
+GDV_DEV gdv_int32 gdv_utf8_char_len(const gdv_uint8* p, gdv_int32 i, gdv_int32 len) {
+  const gdv_int32 cl = gdv_utf8_declared_len(p[i]);
+  if (cl == 0 || i + cl > len) return 0;
+  for (gdv_int32 j = 1; j < cl; j++)
+    if ((p[i + j] & 0xC0) != 0x80) return 0;
+  return cl;
+}
+GDV_DEV gdv_uint32 gdv_utf8_key(const gdv_uint8* p, gdv_int32 i, gdv_int32 cl, gdv_uint8 first) {
+  gdv_uint32 k = first;
+  for (gdv_int32 j = 1; j < cl; j++) k |= (gdv_uint32)p[i + j] << (8 * j);
+  return k;
+}
+// entry of `key` in a kind-1 table, or nullptr
+GDV_DEV const gdv_uint32* gdv_tr_find(const gdv_uint8* desc, gdv_uint32 key) {
+  const gdv_int32 cnt = ((const gdv_int32*)desc)[1];
+  const gdv_uint32* e = (const gdv_uint32*)(desc + 16);
+  for (gdv_int32 k = 0; k < cnt; k++, e += 4)
+    if (e[0] == key) return e;
+  return nullptr;
+}
+GDV_DEV gdv_str gdv_translate(gdv_ctx ctx, gdv_str s, const gdv_uint8* desc) {
+  if (s.len <= 0) return s;
+  const gdv_int32 kind = ((const gdv_int32*)desc)[0], cm = s.map & GDV_MAP_CASE;
+  const gdv_uint8* amap = desc + 16;
+  gdv_int64 out = 0;
+  for (gdv_int32 i = 0; i < s.len;) {
+    const gdv_uint8 c = gdv_map_byte(s.p[i], cm);
+    gdv_int32 cl = 1;
+    if (c >= 0x80) {
+      cl = gdv_utf8_char_len(s.p, i, s.len);
+      if (cl == 0) {
+        gdv_raise(ctx, GDV_ERR_BAD_ARG);
+        s.len = 0;
+        return s;
+      }
+    }
+    if (kind == 0) {
+      out += (c < 0x80 && amap[c] == GDV_TR_DELETE) ? 0 : cl;
+    } else {
+      const gdv_uint32* e = gdv_tr_find(desc, gdv_utf8_key(s.p, i, cl, c));
+      out += e != nullptr ? (gdv_int64)e[1] : cl;
+    }
+    i += cl;
+  }
+  if (out > 0x7fffffffll) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    s.len = 0;
+    return s;
+  }
+  s.lead = (gdv_uint64)s.len;
+  s.lead_p = desc;
+  s.flags = 0;
+  s.len = (gdv_int32)out;
+  s.map = cm | GDV_MAP_TRANSLATE;
+  return s;
+}
+// (byte loop; never writes more than the row function's length)
+template <typename P>
+GDV_DEV void gdv_copy_translated(P dst, const gdv_str& s) {
+  const gdv_uint8* desc = s.lead_p;
+  const gdv_int32 kind = ((const gdv_int32*)desc)[0], len = (gdv_int32)s.lead, cm = s.map & GDV_MAP_CASE, cap = s.len;
+  const gdv_uint8* amap = desc + 16;
+  gdv_int32 o = 0;
+  for (gdv_int32 i = 0; i < len;) {
+    const gdv_uint8 c = gdv_map_byte(s.p[i], cm);
+    gdv_int32 cl = 1;
+    if (c >= 0x80) cl = gdv_utf8_char_len(s.p, i, len);
+    if (cl == 0) return;  // (the row function raised: never reached with a length)
+    const gdv_uint8* rep = nullptr;
+    gdv_int32 rl = -1;
+    if (kind == 0) {
+      if (c < 0x80) {
+        const gdv_uint8 b = amap[c];
+        if (b != GDV_TR_DELETE) {
+          if (o >= cap) return;
+          dst[o++] = b;
+        }
+        i++;
+        continue;
+      }
+    } else {
+      const gdv_uint32* e = gdv_tr_find(desc, gdv_utf8_key(s.p, i, cl, c));
+      if (e != nullptr) {
+        rep = desc + e[2];
+        rl = (gdv_int32)e[1];
+      }
+    }
+    if (rl < 0) {
+      if (o + cl > cap) return;
+      dst[o++] = c;
+      for (gdv_int32 j = 1; j < cl; j++) dst[o++] = s.p[i + j];
+    } else {
+      if (o + rl > cap) return;
+      for (gdv_int32 j = 0; j < rl; j++) dst[o++] = rep[j];
+    }
+    i += cl;
+  }
+}
+// the copy entry points of plans that hold a translate(): translate values here, everything else as before
+GDV_DEV void gdv_str_copy_ext(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_TRANSLATE) {
+    gdv_copy_translated(dst, s);
+    return;
+  }
+  gdv_str_copy(dst, s);
+}
+
 #ifndef GDV_HOST_BUILD
 // the value the NEXT lane holds (lane 63 gets 0): DPP wave_shl:1, no LDS traffic
 GDV_DEV gdv_uint64 gdv_next_lane(gdv_uint64 v) {
@@ -3090,6 +3314,31 @@ GDV_DEV void gdv_stage_copy_mirh(gdv_lds_u8* dst, const gdv_str& s, const gdv_ld
     return;
   }
   gdv_stage_copy_mir(dst, s, mir, mbase, mlen);
+}
+
+// the staged copies of plans that hold a translate() (gdv_str_copy_ext's counterparts)
+GDV_DEV void gdv_stage_copy_ext(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_TRANSLATE) {
+    gdv_copy_translated(dst, s);
+    return;
+  }
+  gdv_stage_copy(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_ext(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                    gdv_int32 mlen) {
+  if (s.map & GDV_MAP_TRANSLATE) {
+    gdv_copy_translated(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_ext(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                     gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_TRANSLATE) {
+    gdv_copy_translated(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh(dst, s, mir, mbase, mlen, bm);
 }
 
 // ------------------------------------------------------------------ small-batch filter: scan + emission in the predicate's own workgroup

@@ -516,6 +516,10 @@ class CodeGen {
                                    // (main kernel: and mirrored in LDS)
   bool replace_hits_ = false;      // wave kernels: replace() over a whole column row may be answered by the sweep
   int replace_hook_ = -1;          // ... the hook (match bitmap) that does
+  bool translate_ = false;         // a translate() value is copied: the plan's copies take the *_ext entry points
+  // the output copy of a var-len value (the *_ext entry: translate values; only plans that hold one use it)
+  std::string CopyFn() const { return translate_ ? "gdv_str_copy_ext" : "gdv_str_copy"; }
+  std::string StageCopyFn(const std::string& base) const { return translate_ ? base + "_ext" : base; }
   std::ostringstream body_;
   std::map<std::string, std::string> cse_;
   int next_tmp_ = 0;
@@ -540,6 +544,64 @@ class CodeGen {
     return static_cast<int>(contains_hooks_.size()) - 1;
   }
 };
+
+// the constant-block table of translate(text, from, to) (layout: gdv_device_lib.hpp, GDV_MAP_TRANSLATE).  Characters of
+// from / to are runs that start at a byte that is not 10xxxxxx; the first occurrence of a character in `from` wins.
+void TranslateTable(const std::string& from, const std::string& to, std::string* tab) {
+  auto chars = [](const std::string& t) {
+    std::vector<std::string> out;
+    for (unsigned char c : t) {
+      if (out.empty() || (c & 0xC0) != 0x80) out.emplace_back();
+      out.back().push_back(static_cast<char>(c));
+    }
+    return out;
+  };
+  const std::vector<std::string> fc = chars(from), tc = chars(to);
+  bool ascii = true;
+  for (unsigned char c : from + to) ascii = ascii && c < 0x80;
+  auto put32 = [](std::string* t, uint32_t v) { t->append(reinterpret_cast<const char*>(&v), 4); };
+  tab->clear();
+  if (ascii) {
+    put32(tab, 0);
+    put32(tab, 0);
+    tab->append(8, '\0');
+    std::string m(256, '\0');
+    std::vector<bool> seen(128, false);
+    for (int c = 0; c < 256; c++) m[c] = static_cast<char>(c);
+    for (size_t i = 0; i < fc.size(); i++) {
+      const unsigned char c = static_cast<unsigned char>(fc[i][0]);
+      if (seen[c]) continue;
+      seen[c] = true;
+      m[c] = i < tc.size() ? tc[i][0] : static_cast<char>(0xFF);  // GDV_TR_DELETE
+    }
+    *tab += m;
+    return;
+  }
+  // kind 1: entries (key, replacement length, replacement offset, unused), then the replacement bytes.  A run of more than
+  // four bytes is no well-formed character: it matches nothing (but keeps its position)
+  std::vector<std::pair<uint32_t, std::string>> entries;
+  std::set<uint32_t> seen;
+  for (size_t i = 0; i < fc.size(); i++) {
+    if (fc[i].size() > 4) continue;
+    uint32_t key = 0;
+    for (size_t j = 0; j < fc[i].size(); j++) key |= static_cast<uint32_t>(static_cast<unsigned char>(fc[i][j])) << (8 * j);
+    if (!seen.insert(key).second) continue;
+    entries.emplace_back(key, i < tc.size() ? tc[i] : std::string());
+  }
+  put32(tab, 1);
+  put32(tab, static_cast<uint32_t>(entries.size()));
+  tab->append(8, '\0');
+  uint32_t at = 16 + 16 * static_cast<uint32_t>(entries.size());
+  std::string bytes;
+  for (auto& e : entries) {
+    put32(tab, e.first);
+    put32(tab, static_cast<uint32_t>(e.second.size()));
+    put32(tab, at + static_cast<uint32_t>(bytes.size()));
+    put32(tab, 0);
+    bytes += e.second;
+  }
+  *tab += bytes;
+}
 
 // functions whose fast path is "the string is pure ASCII" (character index == byte index)
 bool WantsAsciiHint(const std::string& name) {
@@ -646,6 +708,7 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       const bool digest = fn.name().compare(0, 4, "hash") == 0 ? fn.return_type().is_varlen()
                                                                 : (fn.name() == "sha256" || fn.name() == "sha1" || fn.name() == "sha" || fn.name() == "md5");
       out->opaque = fn.name() == "reverse" || fn.name() == "replace" || fn.name() == "initcap" || digest ||
+                    fn.name() == "repeat" || fn.name() == "space" || fn.name() == "translate" ||
                     (fn.name() == "castVARCHAR" && !args[0].type.is_varlen());
       if ((fn.name() == "upper" || fn.name() == "lower") && args.size() == 1 && args[0].col_slot >= 0) {
         out->col_slot = args[0].col_slot;
@@ -729,6 +792,37 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
           }
         }
         out->v = Tmp("gdv_str", guard + " ? gdv_replace(ctx, " + args[0].v + ", " + ByteTable(tab) + ") : gdv_empty_str()");
+        return Status::OK();
+      }
+      if (fn.name() == "translate") {
+        // translate(text, from, to) with LITERAL from / to: the character table is built here, once per expression, into the
+        // constant block (gdv_device_lib.hpp lays it out); the row computes the length, the output copy writes
+        if (fn.children()[1]->kind() != NodeKind::kLiteral || fn.children()[2]->kind() != NodeKind::kLiteral)
+          return Status::CodeGenError("Function " + fn.ToString() + " not supported yet: the HIP backend takes translate "
+                                      "with literal from and to strings only (its character table is built when the "
+                                      "expression is compiled). ");
+        auto& lf = static_cast<const LiteralNode&>(*fn.children()[1]);
+        auto& lt = static_cast<const LiteralNode&>(*fn.children()[2]);
+        if (lf.is_null() || lt.is_null()) {
+          out->vcols = args[0].vcols;
+          out->opaque = false;
+          out->vlane = "false";
+          out->v = "gdv_empty_str()";
+          return Status::OK();
+        }
+        if (lf.value().bytes.empty()) {  // nothing to translate: the text itself
+          *out = args[0];
+          out->type = fn.return_type();
+          return Status::OK();
+        }
+        std::string tab;
+        TranslateTable(lf.value().bytes, lt.value().bytes, &tab);
+        out->vcols = args[0].vcols;
+        out->vlane = args[0].vlane;
+        can_raise_ = true;
+        translate_ = true;
+        const std::string guard = AndExpr(AndExpr("live", active), LaneValid(*out));
+        out->v = Tmp("gdv_str", guard + " ? gdv_translate(ctx, " + args[0].v + ", " + ByteTable(tab) + ") : gdv_empty_str()");
         return Status::OK();
       }
       if (fn.name() == "lpad" || fn.name() == "rpad") {
@@ -2023,7 +2117,7 @@ Status AssembleStrings(CodeGen& cg, KernelPlan* plan, const std::vector<std::str
     << "#define GDV_HIT_WORDS (GDV_SPAN_MAX / 64 + 4)\n"
     << "constexpr bool FULL = false;  // string tiles test `live` at run time (one code path)\n"
     << "#define GDV_OPTFLAT GDV_OPTFLAT_VALUE\n"
-    << "#define GDV_STAGE_COPY(dst, v) gdv_stage_copy(dst, v)\n"
+    << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n"
     << AblDefine()
     << "#define GDV_OUT(e, v) if (live) "
     << (plan->opts.nontemporal ? "gdv_stnt" : "gdv_st") << "(out##e, row, (v))\n";
@@ -2259,11 +2353,11 @@ Status AssembleStringsWave(CodeGen& cg, KernelPlan* plan, const std::vector<std:
     const std::string M = std::to_string(mirror_slot);
     const std::string where = "mir" + M + ", sd" + M + " + sb" + M + ", hm_ok" + M + " ? se" + M + " - sb" + M + " : 0";
     if (cg.replace_hook_ >= 0)
-      s << "#define GDV_STAGE_COPY(dst, v) gdv_stage_copy_mirh(dst, v, " << where << ", hit" << cg.replace_hook_ << ")\n";
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mirh") << "(dst, v, " << where << ", hit" << cg.replace_hook_ << ")\n";
     else
-      s << "#define GDV_STAGE_COPY(dst, v) gdv_stage_copy_mir(dst, v, " << where << ")\n";
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mir") << "(dst, v, " << where << ")\n";
   } else {
-    s << "#define GDV_STAGE_COPY(dst, v) gdv_stage_copy(dst, v)\n";
+    s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n";
   }
 
   s << "GDV_DEV void gdv_tile(const gdv_args& A, const gdv_int64 wt, const int lane, const int wave,\n"
@@ -2492,7 +2586,7 @@ bool ByteFree(const Node& n) {
   static const std::set<std::string> over_strings = {
       "substr", "substring", "left", "right", "upper", "lower", "octet_length", "bit_length", "char_length",
       "length", "lengthUtf8", "castVARCHAR", "concat", "concatOperator", "reverse", "initcap", "lpad", "rpad", "isnull", "hashSHA256", "sha256",
-      "hashSHA1", "sha1", "sha", "hashMD5", "md5",
+      "hashSHA1", "sha1", "sha", "hashMD5", "md5", "repeat",
       "isnotnull"};
   switch (n.kind()) {
     case NodeKind::kField:
@@ -2664,7 +2758,7 @@ Status PlanProjectorShape(const Schema& schema, const std::vector<ExpressionPtr>
         }
         cg.Stmt("  gdv_uint8* at = outd" + E + " + base" + E + " + loc" + E + ";");
         for (auto& name : pv) {
-          cg.Stmt("  if (" + name + ".len > 0) gdv_str_copy(at, " + name + ");");
+          cg.Stmt("  if (" + name + ".len > 0) " + cg.CopyFn() + "(at, " + name + ");");
           cg.Stmt("  at += " + name + ".len;");
         }
         if (has_window) {
@@ -2725,7 +2819,7 @@ Status PlanProjectorShape(const Schema& schema, const std::vector<ExpressionPtr>
         cg.Stmt("} else if (dir" + E + ") {");
         cg.Stmt("  gdv_uint8* at = outd" + E + " + dbase" + E + " + lc" + E + "[0];");
         for (auto& name : pv) {
-          cg.Stmt("  if (" + name + ".len > 0) gdv_str_copy(at, " + name + ");");
+          cg.Stmt("  if (" + name + ".len > 0) " + cg.CopyFn() + "(at, " + name + ");");
           cg.Stmt("  at += " + name + ".len;");
         }
         cg.Stmt("}");
@@ -3434,7 +3528,8 @@ bool MaterialisesBytes(const Node& n) {
   auto& fn = static_cast<const FunctionNode&>(n);
   const std::string& f = fn.name();
   if (f == "concat" || f == "concatOperator" || f == "lpad" || f == "rpad" || f == "reverse" || f == "replace" || f == "initcap" ||
-      f == "hashSHA256" || f == "sha256" || f == "hashSHA1" || f == "sha1" || f == "sha" || f == "hashMD5" || f == "md5")
+      f == "hashSHA256" || f == "sha256" || f == "hashSHA1" || f == "sha1" || f == "sha" || f == "hashMD5" || f == "md5" ||
+      f == "repeat" || f == "space" || f == "translate")
     return true;
   return f == "castVARCHAR" && !fn.children().empty() && !fn.children()[0]->return_type().is_varlen();
 }

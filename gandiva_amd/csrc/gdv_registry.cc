@@ -343,6 +343,15 @@ FunctionRegistry::FunctionRegistry() {
     add(f, {utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_pad");
     add(f, {utf8(), int32(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_pad");
   }
+  // split_part / substring_index: narrower views of the text; repeat / space: cyclic views; translate (literal from / to
+  // only): a table built at Make time, materialised by the output copy.  [recalled semantics: PARITY.md, string tail]
+  add("split_part", {utf8(), utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("substring_index", {utf8(), utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("repeat", {utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("space", {int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("space", {int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("translate", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext,
+      "gdv_translate");  // planned by gdv_planner.cc
   add("locate", {utf8(), utf8()}, int32(), NullPolicy::kNullIfNull, kNeedsContext);
   add("locate", {utf8(), utf8(), int32()}, int32(), NullPolicy::kNullIfNull, kNeedsContext);
   add("position", {utf8(), utf8()}, int32(), NullPolicy::kNullIfNull, kNeedsContext, Sym("locate", {utf8(), utf8()}));
