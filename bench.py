@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
-"""Headline benchmark: BASELINE.json's metric on BASELINE.json's config — and, in the same line ("workloads"), the
-other BASELINE configs (C1, C3, C4, C5) and the fused filter -> project (K2F), each timed, verified and priced
-against the roofline by the same run (round 6).
+"""Headline benchmark: BASELINE.json's metric on BASELINE.json's config — and, with --full, in the same line
+("workloads"), the other BASELINE configs (C1, C3, C4, C5) and the fused filter -> project (K2F), each timed, verified
+and priced against the roofline by the same run (round 6).
+
+  plain    (the default) only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+           Its `roofline` is priced on the timed steps' own HIP events; `verified` is null.
+  --full   everything else as well: the outputs checked against torch, box telemetry during the timed loop, the
+           measured HBM ceilings, `cpu_baseline` and (default invocation) the "workloads" sub-lines.
 
   metric   million rows/s (+ achieved HBM GB/s in `roofline`) of the 10-expression float64
            Projector with 10 % nulls per column (config C2), 2^28 rows PER GPU.
@@ -16,10 +21,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
   roofline      algorithmic bytes (113.75 B/row: every input read once, every output
                 written once, bitmaps at 1 bit/row) / mean kernel time measured with HIP
                 events on the launch stream, against the 8 TB/s HBM3E peak
-  cpu_baseline  the CPU restatement (oracle/, "port") timed on this host's cores on a
+  cpu_baseline  (--full) the CPU restatement (oracle/, "port") timed on this host's cores on a
                 bounded prefix of the same workload.
 
-One workload alone (for profiling):  --workload c3 | c4 | c5 | k2f | c1      --no-extras: the headline without "workloads"
+One workload alone (for profiling):  --workload c3 | c4 | c5 | k2f | c1      --full --no-extras: the headline without "workloads"
 """
 import argparse
 import json
@@ -40,8 +45,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c4", "c5", "k2f"])
     p.add_argument("--rows", type=int, default=0, help="rows per GPU (default: BASELINE size)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need: the outputs of the timed loop against "
+                        "torch, box telemetry, the measured HBM ceilings, the cpu_baseline and (default invocation) the "
+                        "'workloads' sub-lines.  Without it a run sets up, warms up, times, dumps and prints its line")
     p.add_argument("--cpu-rows", type=int, default=1 << 26, help="rows of the cpu_baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the cpu_baseline")
     p.add_argument("--inproc", action="store_true",
                    help="ONE process, --gpus host threads, each on its own device context (round 3: "
                         "in-process multi-device; virtual contexts when the box has fewer GPUs). c2 only")
@@ -59,12 +68,13 @@ def parse():
                         "buffers moves a C2 step between 4.9 and 7.0 ms, and stays with the buffers); 1 = off (the default since round 6: "
                         "the library's pool does the search, --pool-candidates)")
     p.add_argument("--no-verify", action="store_true",
-                   help="skip the post-loop check of the outputs the timed loop produced")
+                   help="with --full: skip the post-loop check of the outputs the timed loop produced")
     p.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                    help="weak: --rows per GPU (default); strong: ONE logical batch of --rows rows (default: BASELINE's size "
                         "for the workload: C2 2^28, C3 10^9, C4 6*10^9) row-sharded across the ranks by gandiva_amd.shard")
     p.add_argument("--no-extras", action="store_true",
-                   help="default invocation only: leave out the 'workloads' object (the other BASELINE configs + K2F)")
+                   help="default invocation only: leave out the 'workloads' object (the other BASELINE configs + K2F) of "
+                        "--full, and their arrays of --dump-outputs")
     p.add_argument("--extras", default="c1,c3,k2f,c5,c4", help="sub-workloads of the default line, in this order")
     p.add_argument("--sub-steps", type=int, default=30)
     p.add_argument("--sub-warmup", type=int, default=3)
@@ -78,7 +88,8 @@ def parse():
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64 / "
                         "float32): a fixed, seeded sample of rows of every output, values and validity; the sub-workloads "
-                        "of the default line as DIR/<workload>_<name>.npy.  Rank 0's shard only.  At most 64 MB in all")
+                        "of the default line as DIR/<workload>_<name>.npy (without --full: what one untimed evaluation "
+                        "over their inputs computes).  Rank 0's shard only.  At most 64 MB in all")
     args = p.parse_args()
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
@@ -1000,8 +1011,10 @@ def timed_loop(wl, steps, warmup, barrier=None, prewarm_s=0.4, sampler=None):
     return elapsed, [s.elapsed_time(e) for s, e in zip(starts, ends)], prewarm
 
 
-def verify(wl, no_verify):
-    if no_verify:
+def verify(wl, args):
+    if not args.full:
+        return {"ok": None, "what": "not checked: a plain run (--full checks the outputs against torch)"}
+    if args.no_verify:
         return {"ok": None, "what": "skipped (--no-verify)"}
     try:
         return verify_outputs(wl.name, wl.rows, wl.dbatch, wl.result())
@@ -1110,7 +1123,7 @@ def sub_line(name, args):
     elapsed, dev_ms, prewarm = timed_loop(wl, args.sub_steps, args.sub_warmup, prewarm_s=0.25)
     if args.dump_outputs:
         args.dump_left -= dump_outputs(wl, args.dump_outputs, prefix=name + "_", budget=args.dump_left)
-    verification = verify(wl, args.no_verify)
+    verification = verify(wl, args)
     roof, achieved, mean_ms = roofline_of(wl, dev_ms, trials, True, placement)
     metric, dtype, text = WORKLOAD_TEXT[name]
     line = {
@@ -1139,6 +1152,16 @@ def sub_line(name, args):
                                     "sample": f"failed: {e}"}
     line["wall_s"] = round(time.perf_counter() - t_wall, 1)
     return line
+
+
+def dump_sub_outputs(name, args):
+    """--dump-outputs of a sub-workload in a plain run: its inputs set up and evaluated once (setup_workload), the same
+    arrays its timed steps leave under --full (same seeded inputs, deterministic kernels), nothing timed or checked."""
+    import torch
+    wl = setup_workload(name, DEFAULT_ROWS[name], args)
+    args.dump_left -= dump_outputs(wl, args.dump_outputs, prefix=name + "_", budget=args.dump_left)
+    del wl
+    torch.cuda.empty_cache()
 
 
 def main():
@@ -1198,21 +1221,23 @@ def main():
     placement = pool_outputs(wl, args.pool_candidates)
     placement_trials = search_placements(wl, args.placements)
 
-    try:
-        bus = torch.cuda.get_device_properties(device_index).pci_bus_id
-        bus_id = f"{int(bus):02x}:" if isinstance(bus, int) else str(bus)
-    except Exception:
-        bus_id = None
-    sampler = BoxSampler(bus_id if rank == 0 else None) if rank == 0 and os.environ.get("GDV_BENCH_NO_TELEMETRY") is None else None
-    if sampler is not None and sampler.dev is None:
-        sampler = BoxSampler(None)   # bus id did not match a sysfs path: take the first amdgpu card
+    sampler = None
+    if args.full and rank == 0 and os.environ.get("GDV_BENCH_NO_TELEMETRY") is None:
+        try:
+            bus = torch.cuda.get_device_properties(device_index).pci_bus_id
+            bus_id = f"{int(bus):02x}:" if isinstance(bus, int) else str(bus)
+        except Exception:
+            bus_id = None
+        sampler = BoxSampler(bus_id)
+        if sampler.dev is None:
+            sampler = BoxSampler(None)   # bus id did not match a sysfs path: take the first amdgpu card
     elapsed, dev_ms, prewarm = timed_loop(wl, args.steps, args.warmup, barrier=barrier, sampler=sampler)
     # what the last timed step computed, before anything else touches the outputs (rank 0's shard)
     if args.dump_outputs and rank == 0:
         args.dump_left = DUMP_LIMIT_BYTES - dump_outputs(wl, args.dump_outputs)
 
-    # what did the timed loop leave behind?  (outside the timed region; every rank checks its own shard)
-    verification = verify(wl, args.no_verify)
+    # what did the timed loop leave behind?  (--full, outside the timed region; every rank checks its own shard)
+    verification = verify(wl, args)
     bad = 0.0 if verification["ok"] in (True, None) else 1.0
 
     roof, achieved, mean_dev_ms = roofline_of(wl, dev_ms, placement_trials, not args.rows and not strong, placement)
@@ -1247,7 +1272,7 @@ def main():
             "vs_baseline": None,
             "dtype": dtype,
             "data": "synthetic",
-            "verified": (None if args.no_verify else not any_rank_failed),
+            "verified": (None if verification["ok"] is None else not any_rank_failed),
             "verification": verification if not any_rank_failed or not verification["ok"] else
                             {"ok": False, "what": "another rank's check failed"},
             "config": {
@@ -1264,59 +1289,61 @@ def main():
             },
             "roofline": roof,
         }
-        # the box this number was taken on: telemetry during the timed loop + what plain streaming
-        # kernels reach here, now, in this process
-        box = sampler.summary() if sampler else {}
-        ceil = None
-        try:
-            torch.cuda.synchronize()
-            ceil = hbm_ceilings()
-        except Exception as e:  # never take the bench line down
-            box["ceiling_error"] = str(e)
-        shaped = None
-        try:
-            if args.workload == "c2":
-                # the headline: the ceiling is taken on the very buffers the timed loop read and wrote
-                shaped = stream_ceiling_on([c.data for c in wl.dbatch.columns], [o.data for o in wl.outs], rows)
-            else:
-                nr, nw = CEILING_SHAPE[args.workload]
-                per_stream = max(1 << 28, min(1 << 32, int(wl.bytes_per_row * rows / (nr + nw)) & ~8191))
-                shaped = stream_ceiling(nr, nw, per_stream)
-        except Exception as e:
-            box["ceiling_error"] = str(e)
-        if ceil:
-            box["ceiling"] = ceil
-            rshare = wl.read_per_row / wl.bytes_per_row
-            mixed = 1.0 / (rshare / ceil["read"] + (1.0 - rshare) / ceil["write"])
-            box["ceiling_for_this_read_write_mix"] = round(mixed, 1)
-            # the ceiling = the best ANY of the streaming instruments reaches for this traffic: the
-            # shape-matched kernel (same number of input / output streams as the workload, grid and
-            # non-temporal flag swept) or the one-stream read / write rates combined for the mix
-            best = max(mixed, shaped["GB/s"] if shaped else 0.0)
-            if shaped:
-                box["ceiling_same_shape"] = shaped
-            if achieved > best:
-                # the product kernel outran every streaming instrument of this run (a fraction of a percent, run-to-run
-                # noise between two kernels of the same shape): the ceiling is then what the product reached
-                box["ceiling_raised_to_the_product_kernel"] = True
-                best = achieved
-            line["roofline"]["measured_ceiling"] = round(best, 1)
-            line["roofline"]["frac_of_measured_ceiling"] = round(achieved / best, 4)
-        line["roofline"]["box"] = box
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # the box this number was taken on: telemetry during the timed loop + what plain streaming
+            # kernels reach here, now, in this process
+            box = sampler.summary() if sampler else {}
+            ceil = None
+            try:
+                torch.cuda.synchronize()
+                ceil = hbm_ceilings()
+            except Exception as e:  # never take the bench line down
+                box["ceiling_error"] = str(e)
+            shaped = None
             try:
                 if args.workload == "c2":
-                    line["cpu_baseline"] = cpu_baseline_c2(args.cpu_rows)
+                    # the headline: the ceiling is taken on the very buffers the timed loop read and wrote
+                    shaped = stream_ceiling_on([c.data for c in wl.dbatch.columns], [o.data for o in wl.outs], rows)
                 else:
-                    line["cpu_baseline"] = short_cpu_baseline(args.workload, 8.0)
-            except Exception as e:  # the baseline must never take the bench line down
-                line["cpu_baseline"] = {"value": None, "unit": "million rows/s", "cores": 0,
-                                        "kind": "port", "sample": f"failed: {e}"}
+                    nr, nw = CEILING_SHAPE[args.workload]
+                    per_stream = max(1 << 28, min(1 << 32, int(wl.bytes_per_row * rows / (nr + nw)) & ~8191))
+                    shaped = stream_ceiling(nr, nw, per_stream)
+            except Exception as e:
+                box["ceiling_error"] = str(e)
+            if ceil:
+                box["ceiling"] = ceil
+                rshare = wl.read_per_row / wl.bytes_per_row
+                mixed = 1.0 / (rshare / ceil["read"] + (1.0 - rshare) / ceil["write"])
+                box["ceiling_for_this_read_write_mix"] = round(mixed, 1)
+                # the ceiling = the best ANY of the streaming instruments reaches for this traffic: the
+                # shape-matched kernel (same number of input / output streams as the workload, grid and
+                # non-temporal flag swept) or the one-stream read / write rates combined for the mix
+                best = max(mixed, shaped["GB/s"] if shaped else 0.0)
+                if shaped:
+                    box["ceiling_same_shape"] = shaped
+                if achieved > best:
+                    # the product kernel outran every streaming instrument of this run (a fraction of a percent, run-to-run
+                    # noise between two kernels of the same shape): the ceiling is then what the product reached
+                    box["ceiling_raised_to_the_product_kernel"] = True
+                    best = achieved
+                line["roofline"]["measured_ceiling"] = round(best, 1)
+                line["roofline"]["frac_of_measured_ceiling"] = round(achieved / best, 4)
+            line["roofline"]["box"] = box
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    if args.workload == "c2":
+                        line["cpu_baseline"] = cpu_baseline_c2(args.cpu_rows)
+                    else:
+                        line["cpu_baseline"] = short_cpu_baseline(args.workload, 8.0)
+                except Exception as e:  # the baseline must never take the bench line down
+                    line["cpu_baseline"] = {"value": None, "unit": "million rows/s", "cores": 0,
+                                            "kind": "port", "sample": f"failed: {e}"}
         # Round 6: the other BASELINE configs (and the fused filter -> project) in the SAME line, so that the driver's
         # one run times them all: "workloads": {c1, c3, k2f, c5, c4} — each with ms_per_step, kernel_ms (HIP events),
         # kernel names, roofline.frac on §8(d)'s algorithmic bytes, PMC traffic where a pass on the running kernel is
         # committed, verified, and a short cpu_baseline.  Only for the default invocation (one GPU, C2, BASELINE size).
-        if world == 1 and args.workload == "c2" and not args.rows and not strong and not args.no_extras:
+        default_line = world == 1 and args.workload == "c2" and not args.rows and not strong and not args.no_extras
+        if args.full and default_line:
             del wl
             torch.cuda.empty_cache()
             subs = {}
@@ -1332,9 +1359,17 @@ def main():
                 verification = {"ok": False, "what": "a sub-workload failed: " + ", ".join(
                     k for k, v in subs.items() if not v.get("verified"))}
                 line["verified"] = False
+        elif args.dump_outputs and default_line:
+            # a plain run writes the same files as --full: the sub-workloads' outputs come from one untimed evaluation each
+            del wl
+            torch.cuda.empty_cache()
+            for name in args.extras.split(","):
+                dump_sub_outputs(name, args)
         if args.dump_outputs:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": DUMP_LIMIT_BYTES - args.dump_left,
-                                      "of": "the last timed step of every workload in this line (a seeded sample of rows)"}
+                                      "of": "the last timed step of every workload in this line (a seeded sample of rows)" if args.full else
+                                            "the last timed step (a seeded sample of rows); the default line's sub-workloads: "
+                                            "one untimed evaluation each"}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -26,6 +26,19 @@ def test_defaults_are_the_drivers_invocation_and_every_workload_is_described(mon
     assert bench.STRONG_ROWS["c4"] == 6 * 10**9 and bench.DEFAULT_ROWS["c4"] * 8 == bench.STRONG_ROWS["c4"]
 
 
+def test_a_plain_run_checks_nothing_and_full_is_opt_in(monkeypatch):
+    """Without --full the bench sets up, warms up, times, dumps and prints: its outputs are not checked (the workload is
+    not even looked at); --full checks them unless --no-verify."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False
+    assert bench.verify(None, a)["ok"] is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-verify"])
+    a = bench.parse()
+    assert a.full is True and bench.verify(None, a) == {"ok": None, "what": "skipped (--no-verify)"}
+
+
 def test_short_cpu_baselines_run_on_bounded_samples():
     bench = _bench()
     for name in ("c1", "c3", "k2f", "c4", "c5"):

@@ -179,7 +179,7 @@ def test_bench_launches_the_ranks_it_is_asked_for_and_verifies_what_it_timed():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "1048576", "--steps", "5",
-                        "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["verified"] is True and line["config"]["total_rows"] == 2 * 1048576

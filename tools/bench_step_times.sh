@@ -2,7 +2,7 @@
 # Which earlier workload of the driver's line stretches single steps of a later one?   bash tools/bench_step_times.sh
 cd ${GRAFT_REPO_ROOT:-$PWD}
 for extras in "c5" "k2f,c5" "c3,c5" "c1,c5" "c1,c3,k2f,c5" "c1,c3,k2f,c5,c4"; do
-GDV_BENCH_STEP_TIMES=1 python bench.py --no-cpu-baseline --extras $extras 2>/dev/null | python -c "
+GDV_BENCH_STEP_TIMES=1 python bench.py --full --no-cpu-baseline --extras $extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 out=[]

@@ -2,7 +2,7 @@
 # Round 6: C3's predicate kernel against the two-stream read skeleton (6.85 TB/s at 2 workgroups per CU, 4 sub-tiles, non-temporal;
 # the kernel: 6.07 at 8 per CU, 16 sub-tiles) — grid x sub-tiles x waves, alternating on one box.   bash tools/c3_shape_sweep.sh
 cd ${GRAFT_REPO_ROOT:-$PWD}
-run() { echo "$1: $(env $2 GDV_NO_TIER0=1 python bench.py --workload c3 --no-extras --no-cpu-baseline --data philox --steps 30 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); r=d['roofline']; print(d['ms_per_step'], r['kernel_ms'], d['verified'], r['frac'])")"; }
+run() { echo "$1: $(env $2 GDV_NO_TIER0=1 python bench.py --workload c3 --full --no-extras --no-cpu-baseline --data philox --steps 30 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); r=d['roofline']; print(d['ms_per_step'], r['kernel_ms'], d['verified'], r['frac'])")"; }
 for rep in 1 2 3; do
 run "default (U=16 W=4 grid x8)" ""
 run "grid x2                   " "GDV_GRID_MULT=2"

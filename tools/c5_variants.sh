@@ -8,7 +8,7 @@ cd /tmp
 i=0
 run() {  # name, env assignments...
   local name=$1; shift; i=$((i+1))
-  local ms=$(timeout 200 env "$@" python $R/bench.py --workload c5 --no-cpu-baseline --steps 12 --warmup 3 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['kernel_ms_min'], d['verified'])")
+  local ms=$(timeout 200 env "$@" python $R/bench.py --workload c5 --full --no-cpu-baseline --steps 12 --warmup 3 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['kernel_ms_min'], d['verified'])")
   timeout 200 env "$@" rocprofv3 --kernel-trace --stats -d $OUT/v$i -o c5 --output-format csv -- python $R/bench.py --workload c5 --steps 5 --warmup 2 --no-cpu-baseline --no-verify > /dev/null 2>&1
   local k=$(find $OUT/v$i -name "*kernel_stats.csv" | head -1 | xargs grep "^\"gdv_k_" | awk -F, '{printf "%s=%.1fus ", substr($1,2,12), $4/1000}')
   find $OUT/v$i -name "*kernel_trace.csv" -delete

@@ -37,9 +37,9 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $OUT/smoke.log
 # the driver's own command: C2 headline + every other BASELINE config and K2F under "workloads"
-case " $WL " in *" c2 "*) ( time python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err ) 2> $OUT/bench_c2_time.txt; cut -c1-400 $OUT/bench_c2.json;; esac
+case " $WL " in *" c2 "*) ( time python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err ) 2> $OUT/bench_c2_time.txt; cut -c1-400 $OUT/bench_c2.json;; esac
 [ -z "$WORKLOADS" ] && BENCH_WL="$WL c1" || BENCH_WL="$WL"
-for w in c1 c3 c4 c5 k2f; do case " $BENCH_WL " in *" $w "*) python bench.py --workload $w --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err;; esac; done
+for w in c1 c3 c4 c5 k2f; do case " $BENCH_WL " in *" $w "*) python bench.py --workload $w --full --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err;; esac; done
 cd /tmp
 for w in $WL; do
   rocprofv3 --kernel-trace --stats -d $OUT/prof_$w -o $w --output-format csv -- python $R/bench.py --workload $w --no-extras --no-cpu-baseline --no-verify > $OUT/prof_${w}_bench.json 2> /dev/null
@@ -51,8 +51,8 @@ done
 cd $R; python tools/summarize_round.py $ROUND > /dev/null 2>&1
 for w in $WL; do
   if python -c "import json,sys; sys.exit(0 if json.load(open('$OUT/bench_$w.json'))['roofline'].get('traffic') is None else 1)" 2>/dev/null; then
-    if [ $w = c2 ]; then python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-    else python bench.py --workload $w --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err; fi
+    if [ $w = c2 ]; then python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+    else python bench.py --workload $w --full --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err; fi
   fi
 done
 cd /tmp
@@ -83,8 +83,8 @@ grep '^"gdv_k_' $(find $OUT/prof_c5na -name "*kernel_stats.csv" | head -1) | awk
 # in-process multi-device: N host threads over N device contexts (virtual on a one-GPU box)
 for n in 1 2 8; do echo "--inproc --gpus $n: $(timeout 300 python bench.py --inproc --gpus $n --steps 10 --warmup 2 2>&1 | tail -1 | cut -c1-420)"; done > $OUT/inproc_bench.txt
 # the N-rank launch path on this one-GPU box (gloo: the ranks share cuda:0 — control flow, not scaling)
-{ echo "GDV_BENCH_BACKEND=gloo bench.py --gpus 2 --rows 16777216 (weak): $(GDV_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --rows 16777216 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 | cut -c1-700)"
-  for w in c2 c3 c4; do echo "GDV_BENCH_BACKEND=gloo bench.py --gpus 2 --workload $w --scaling strong --rows 33554432: $(GDV_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --workload $w --scaling strong --rows 33554432 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 | cut -c1-700)"; done; } > $OUT/bench_two_ranks.txt
+{ echo "GDV_BENCH_BACKEND=gloo bench.py --gpus 2 --rows 16777216 (weak): $(GDV_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --rows 16777216 --full --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 | cut -c1-700)"
+  for w in c2 c3 c4; do echo "GDV_BENCH_BACKEND=gloo bench.py --gpus 2 --workload $w --scaling strong --rows 33554432: $(GDV_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --workload $w --scaling strong --rows 33554432 --full --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 | cut -c1-700)"; done; } > $OUT/bench_two_ranks.txt
 fi
 if [ -n "$NO_EXTRAS" ]; then case " $WL " in *" c5 "*)
   PYTHONPATH=$R timeout 300 python tools/c5_nonascii.py 2>&1 | grep -v amdgpu.ids > $OUT/c5_nonascii.txt

@@ -107,14 +107,14 @@ with open(os.path.join(DST, ROUND + "_summary.md"), "w") as f:
             tr = f"{pj['traffic_over_algorithmic']:.4f} x" + ("" if pj["kernel"] == r["kernel_name"] else f" (on {pj['kernel'][:22]}: NOT the timed kernel)")
         f.write(f"| {w.upper()} | {d['ms_per_step']} | {r['kernel_ms']} on {r['kernel_name']} | {ks} | "
                 f"{d['value'] / 1e3:.1f} G | {r['achieved'] / 1e3:.2f} TB/s | {r['frac']} | {r.get('frac_of_measured_ceiling', '-')} | {tr} | {(('pool: ' + str(r['placement']['sets'][0]['rates_gbs']) + ' GB/s, first plain allocation ' + str(r.get('frac_first_plain_allocation'))) if r.get('placement') else None) or r.get('placement_trials_ms') or '-'} |\n")
-    # the driver's own command (python bench.py): the sub-lines of the ONE bench line
+    # the driver's own command (python bench.py --full): the sub-lines of the ONE bench line
     b = os.path.join(DST, f"{ROUND}_c2_bench.json")
     try:
         d = json.loads([l for l in open(b) if l.startswith("{")][-1])
     except Exception:
         d = {}
     if d.get("workloads"):
-        f.write("\n<!-- the sub-lines of the same run's ONE bench line (python bench.py): \"workloads\" -->\n")
+        f.write("\n<!-- the sub-lines of the same run's ONE bench line (python bench.py --full): \"workloads\" -->\n")
         f.write("| in the driver's line | ms_per_step | kernel_ms (HIP events) | frac of 8 TB/s | PMC traffic / algorithmic bytes | verified | cpu_baseline (port) | wall s |\n|---|---|---|---|---|---|---|---|\n")
         f.write(f"| **c2 (headline)** | {d['ms_per_step']} | {d['roofline']['kernel_ms']} | {d['roofline']['frac']} | "
                 f"{(d['roofline']['traffic'] or 0) / (d['roofline']['algorithmic_bytes_per_row'] * d['config']['rows_per_gpu']):.4f} | {d['verified']} | "
