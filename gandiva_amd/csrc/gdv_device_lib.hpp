@@ -3279,6 +3279,333 @@ GDV_DEV void gdv_str_copy_ext(gdv_uint8* dst, const gdv_str& s) {
   gdv_str_copy(dst, s);
 }
 
+// ------------------------------------------------------------------ text <-> date / time: castDATE, castTIMESTAMP, castTIME
+// of text; castVARCHAR of date32, date64, timestamp, time32; castTIME(timestamp), castTIMESTAMP(date32).  Timestamps and times
+// are milliseconds.  Every function is null if null; a row that does not parse raises GDV_ERR_BAD_ARG.
+// [recollection, PARITY.md "text <-> date / time"; the "decided" items are this library's own]
+//   castDATE(text): at most three digit runs (year, month, day), each ended by any one byte that is not a digit (an empty
+//     run is 0); reading stops after the third run's separator.  Fewer than three runs raise.  A year below 100 written with
+//     fewer than 4 digits becomes 20yy when yy < 70, else 19yy.  The date must exist.  [decided: a year above 9999 raises; a
+//     run of more than 9 digits raises]
+//   castTIMESTAMP(text): exactly  Y{1,4} '-' M{1,2} '-' D{1,2} [(' ' | 'T') h{1,2} ':' m{1,2} [':' s{1,2} ['.' f{1,3}]]]
+//     [' '? ('+' | '-') hh [':'? mm]]  read through the text's case map.  Years as castDATE; the fraction scaled to
+//     milliseconds; hour 0..23, minute and second 0..59; an offset +hh:mm (the wall time is that far ahead of UTC) is
+//     subtracted.  [decided: 'T' is accepted; the offset's hour 0..23 and minute 0..59]
+//   castTIME(text): exactly  h{1,2} ':' m{1,2} [':' s{1,2} ['.' f{1,3}]]  -> milliseconds of the day, the same ranges.
+//   castVARCHAR(timestamp, n): "yyyy-MM-dd hh:mm:ss.sss" of the civil UTC time (fields by floor division, so instants
+//     before 1970 show their wall clock), cut to min(n, 23) bytes; date32 / date64: "yyyy-MM-dd", min(n, 10); time32:
+//     "hh:mm:ss.sss", min(n, 12) [decided: of the value modulo one day, floor modulo].  A year outside 0..9999: '-' when
+//     negative, then at least four digits, still cut.  n < 0 raises.  A row's length therefore follows from n alone.
+// Parsers: an INBUF row in a canonical layout (yyyy-MM-dd, yyyy-MM-dd hh:mm:ss, yyyy-MM-dd hh:mm:ss.sss, hh:mm:ss,
+// hh:mm:ss.sss) is checked with two or three 8-byte loads and SWAR masks, its digits taken from the words; any other row
+// takes the byte scanner.  The fast path accepts nothing the scanner rejects and gives the same value.
+// Formatters: a value of its own kind, GDV_MAP_DATETIME (lead = the instant in milliseconds, (map >> 16) & 3 = 0 timestamp,
+// 1 date, 2 time), which is NOT one of GDV_MAP_SPECIAL: only plans that hold one copy their outputs through the *_dt
+// entry points below, which build the text in registers and store it as whole words.
+#define GDV_MAP_DATETIME 16384
+
+// bytes of w at the positions of `dig` (0xFF per byte) are ASCII digits, those at `sep` are as in `pat` (0x30 at digits)
+GDV_DEV bool gdv_dt_layout(gdv_uint64 w, gdv_uint64 dig, gdv_uint64 sep, gdv_uint64 pat) {
+  const gdv_uint64 hi = (w & ((dig & 0xF0F0F0F0F0F0F0F0ull) | sep)) ^ pat;
+  const gdv_uint64 lo = ((w & 0x0F0F0F0F0F0F0F0Full) + 0x0606060606060606ull) & 0x1010101010101010ull & dig;  // low nibble > 9
+  return (hi | lo) == 0;
+}
+// the digit at byte i of w / the two-digit number at bytes i, i + 1
+GDV_DEV gdv_int32 gdv_dt_d1(gdv_uint64 w, int i) { return (gdv_int32)((w >> (8 * i)) & 15); }
+GDV_DEV gdv_int32 gdv_dt_d2(gdv_uint64 w, int i) { return 10 * gdv_dt_d1(w, i) + gdv_dt_d1(w, i + 1); }
+GDV_DEV bool gdv_dt_is_digit(gdv_uint8 c) { return c >= '0' && c <= '9'; }
+GDV_DEV gdv_int64 gdv_dt_year(gdv_int64 y, gdv_int32 ndigits) {
+  return (y < 100 && ndigits < 4) ? (y < 70 ? 2000 + y : 1900 + y) : y;
+}
+// the day number of y-m-d, y in 0..9999; false when there is no such date
+GDV_DEV bool gdv_dt_days(gdv_int64 y, gdv_int32 m, gdv_int32 d, gdv_int64* days) {
+  if (y < 0 || y > 9999 || m < 1 || m > 12 || d < 1 || d > gdv_last_day_of_month(y, m)) return false;
+  *days = gdv_days_from_civil(y, m, d);
+  return true;
+}
+// yyyy-MM-dd in bytes 0..9 (w0 = bytes 0..7, w1 = bytes 8..): 1 and *days, 0 (no such date), -1 (not this layout)
+GDV_DEV int gdv_dt_fast_date(gdv_uint64 w0, gdv_uint64 w1, gdv_int64* days) {
+  if (!gdv_dt_layout(w0, 0x00ffff00ffffffffull, 0xff0000ff00000000ull, 0x2d30302d30303030ull) ||
+      !gdv_dt_layout(w1, 0xffffull, 0, 0x3030ull))
+    return -1;
+  return gdv_dt_days(100 * gdv_dt_d2(w0, 0) + gdv_dt_d2(w0, 2), gdv_dt_d2(w0, 5), gdv_dt_d2(w1, 0), days) ? 1 : 0;
+}
+// the run of digits at byte i: its length (counted to max + 1 at most) and value
+GDV_DEV gdv_int32 gdv_dt_run(const gdv_str& s, gdv_int32 i, gdv_int32 max, gdv_int32* v) {
+  gdv_int32 n = 0, x = 0;
+  for (; i + n < s.len && n <= max && gdv_dt_is_digit(s.p[i + n]); n++) x = 10 * x + (s.p[i + n] - '0');
+  *v = x;
+  return n;
+}
+GDV_DEV bool gdv_dt_at(const gdv_str& s, gdv_int32 i, gdv_uint8 c) { return i < s.len && gdv_str_at(s, i) == c; }
+// castDATE's byte scanner
+GDV_DEV bool gdv_dt_scan_date(const gdv_str& s, gdv_int64* days) {
+  gdv_int32 k = 0, v = 0, n = 0, y = 0, yn = 0, m = 0, d = 0;
+  for (gdv_int32 i = 0; i < s.len && k < 3; i++) {
+    const gdv_uint8 c = s.p[i];
+    if (gdv_dt_is_digit(c)) {
+      if (++n > 9) return false;
+      v = 10 * v + (c - '0');
+      continue;
+    }
+    if (k == 0) { y = v; yn = n; } else if (k == 1) { m = v; } else { d = v; }
+    k++;
+    v = n = 0;
+  }
+  if (k < 3) {  // the last run ends with the text
+    if (k == 0) { y = v; yn = n; } else if (k == 1) { m = v; } else { d = v; }
+    k++;
+  }
+  return k == 3 && gdv_dt_days(gdv_dt_year(y, yn), m, d, days);
+}
+// h{1,2} ':' m{1,2} [':' s{1,2} ['.' f{1,3}]] at byte `at`: the bytes it takes (*ms set), or -1
+GDV_DEV gdv_int32 gdv_dt_scan_clock(const gdv_str& s, gdv_int32 at, gdv_int64* ms) {
+  gdv_int32 i = at, h = 0, mi = 0, sec = 0, f = 0, n = gdv_dt_run(s, i, 2, &h);
+  if (n < 1 || n > 2 || !gdv_dt_at(s, i += n, ':')) return -1;
+  n = gdv_dt_run(s, ++i, 2, &mi);
+  if (n < 1 || n > 2) return -1;
+  i += n;
+  if (gdv_dt_at(s, i, ':')) {
+    n = gdv_dt_run(s, ++i, 2, &sec);
+    if (n < 1 || n > 2) return -1;
+    i += n;
+    if (gdv_dt_at(s, i, '.')) {
+      n = gdv_dt_run(s, ++i, 3, &f);
+      if (n < 1 || n > 3) return -1;
+      i += n;
+      f *= n == 1 ? 100 : n == 2 ? 10 : 1;
+    }
+  }
+  if (h > 23 || mi > 59 || sec > 59) return -1;
+  *ms = h * 3600000ll + mi * 60000ll + sec * 1000ll + f;
+  return i - at;
+}
+// castTIMESTAMP's byte scanner
+GDV_DEV bool gdv_dt_scan_ts(const gdv_str& s, gdv_int64* ms) {
+  gdv_int32 y = 0, m = 0, d = 0, i = 0, n = gdv_dt_run(s, 0, 4, &y);
+  const gdv_int32 yn = n;
+  if (n < 1 || n > 4 || !gdv_dt_at(s, i += n, '-')) return false;
+  n = gdv_dt_run(s, ++i, 2, &m);
+  if (n < 1 || n > 2 || !gdv_dt_at(s, i += n, '-')) return false;
+  n = gdv_dt_run(s, ++i, 2, &d);
+  if (n < 1 || n > 2) return false;
+  i += n;
+  gdv_int64 days = 0, t = 0;
+  if (!gdv_dt_days(gdv_dt_year(y, yn), m, d, &days)) return false;
+  if ((gdv_dt_at(s, i, ' ') || gdv_dt_at(s, i, 'T')) && i + 1 < s.len && gdv_dt_is_digit(s.p[i + 1])) {
+    n = gdv_dt_scan_clock(s, i + 1, &t);
+    if (n < 0) return false;
+    i += 1 + n;
+  }
+  if (i < s.len) {  // the offset
+    if (gdv_dt_at(s, i, ' ')) i++;
+    const bool neg = gdv_dt_at(s, i, '-');
+    if (!neg && !gdv_dt_at(s, i, '+')) return false;
+    gdv_int32 oh = 0, om = 0;
+    n = gdv_dt_run(s, ++i, 4, &oh);
+    if (n == 4) {
+      om = oh % 100;
+      oh /= 100;
+    } else if (n == 2 && gdv_dt_at(s, i + 2, ':')) {
+      n = 3 + gdv_dt_run(s, i + 3, 2, &om);
+      if (n != 5) return false;
+    } else if (n != 2) {
+      return false;
+    }
+    if (i + n != s.len || oh > 23 || om > 59) return false;
+    const gdv_int64 off = oh * 3600000ll + om * 60000ll;
+    t += neg ? off : -off;
+  }
+  *ms = days * GDV_MILLIS_IN_DAY + t;
+  return true;
+}
+GDV_DEV gdv_date64 castDATE_utf8(gdv_ctx ctx, gdv_str s) {
+  gdv_int64 days = 0;
+  int r = -1;
+  if ((s.flags & GDV_STR_INBUF) && s.len >= 10) {
+    const gdv_uint64 w1 = gdv_load8_raw(s.p + 8);
+    if (s.len == 10 || !gdv_dt_is_digit((gdv_uint8)(w1 >> 16))) r = gdv_dt_fast_date(gdv_load8_raw(s.p), w1, &days);
+  }
+  if (r < 0) r = gdv_dt_scan_date(s, &days) ? 1 : 0;
+  if (r == 0) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return 0;
+  }
+  return days * GDV_MILLIS_IN_DAY;
+}
+GDV_DEV gdv_timestamp castTIMESTAMP_utf8(gdv_ctx ctx, gdv_str s) {
+  gdv_int64 ms = 0;
+  int r = -1;
+  if ((s.flags & GDV_STR_INBUF) && (s.len == 10 || s.len == 19 || s.len == 23)) {
+    const gdv_uint64 w0 = gdv_load8_raw(s.p), w1 = gdv_load8_raw(s.p + 8);
+    gdv_int64 days = 0;
+    if (s.len == 10) {
+      r = gdv_dt_fast_date(w0, w1, &days);
+    } else {
+      const gdv_uint64 w2 = gdv_load8_raw(s.p + 16);
+      const bool shape =
+          gdv_dt_layout(w0, 0x00ffff00ffffffffull, 0xff0000ff00000000ull, 0x2d30302d30303030ull) &&
+          gdv_dt_layout(w1, 0xffff00ffff00ffffull, 0x0000ff0000ff0000ull, 0x30303a3030203030ull) &&
+          (s.len == 19 ? gdv_dt_layout(w2, 0xffff00ull, 0xffull, 0x30303aull)
+                       : gdv_dt_layout(w2, 0x00ffffff00ffff00ull, 0x00000000ff0000ffull, 0x003030302e30303aull));
+      if (shape) {
+        const gdv_int32 h = gdv_dt_d2(w1, 3), mi = gdv_dt_d2(w1, 6), sec = gdv_dt_d2(w2, 1);
+        r = gdv_dt_days(100 * gdv_dt_d2(w0, 0) + gdv_dt_d2(w0, 2), gdv_dt_d2(w0, 5), gdv_dt_d2(w1, 0), &days) && h <= 23 &&
+            mi <= 59 && sec <= 59;
+        ms = h * 3600000ll + mi * 60000ll + sec * 1000ll + (s.len == 23 ? 100 * gdv_dt_d1(w2, 4) + gdv_dt_d2(w2, 5) : 0);
+      }
+    }
+    ms += days * GDV_MILLIS_IN_DAY;
+  }
+  if (r < 0) r = gdv_dt_scan_ts(s, &ms) ? 1 : 0;
+  if (r == 0) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return 0;
+  }
+  return ms;
+}
+GDV_DEV gdv_time32 castTIME_utf8(gdv_ctx ctx, gdv_str s) {
+  gdv_int64 ms = 0;
+  int r = -1;
+  if ((s.flags & GDV_STR_INBUF) && (s.len == 8 || s.len == 12)) {
+    const gdv_uint64 w0 = gdv_load8_raw(s.p), w1 = s.len == 12 ? gdv_load8_raw(s.p + 8) : 0ull;
+    if (gdv_dt_layout(w0, 0xffff00ffff00ffffull, 0x0000ff0000ff0000ull, 0x30303a30303a3030ull) &&
+        (s.len == 8 || gdv_dt_layout(w1, 0xffffff00ull, 0xffull, 0x3030302eull))) {
+      const gdv_int32 h = gdv_dt_d2(w0, 0), mi = gdv_dt_d2(w0, 3), sec = gdv_dt_d2(w0, 6);
+      r = h <= 23 && mi <= 59 && sec <= 59;
+      ms = h * 3600000ll + mi * 60000ll + sec * 1000ll + (s.len == 12 ? 100 * gdv_dt_d1(w1, 1) + gdv_dt_d2(w1, 2) : 0);
+    }
+  }
+  if (r < 0) r = gdv_dt_scan_clock(s, 0, &ms) == s.len ? 1 : 0;
+  if (r == 0) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return 0;
+  }
+  return (gdv_time32)ms;
+}
+GDV_DEV gdv_time32 castTIME_timestamp(gdv_timestamp t) {
+  const gdv_int64 r = t % GDV_MILLIS_IN_DAY;
+  return (gdv_time32)(r < 0 ? r + GDV_MILLIS_IN_DAY : r);
+}
+GDV_DEV gdv_timestamp castTIMESTAMP_date32(gdv_date32 d) { return (gdv_int64)d * GDV_MILLIS_IN_DAY; }
+
+GDV_DEV gdv_str gdv_dt_text(gdv_ctx ctx, gdv_int64 ms, gdv_int32 kind, gdv_int32 full, gdv_int64 n) {
+  gdv_str r = gdv_empty_str();
+  if (n < 0) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return r;
+  }
+  r.len = n < full ? (gdv_int32)n : full;
+  r.map = GDV_MAP_DATETIME | (kind << 16);
+  r.flags = 0;
+  r.lead = (gdv_uint64)ms;
+  return r;
+}
+GDV_DEV gdv_str castVARCHAR_timestamp_int64(gdv_ctx ctx, gdv_timestamp v, gdv_int64 n) { return gdv_dt_text(ctx, v, 0, 23, n); }
+GDV_DEV gdv_str castVARCHAR_date64_int64(gdv_ctx ctx, gdv_date64 v, gdv_int64 n) { return gdv_dt_text(ctx, v, 1, 10, n); }
+GDV_DEV gdv_str castVARCHAR_date32_int64(gdv_ctx ctx, gdv_date32 v, gdv_int64 n) {
+  return gdv_dt_text(ctx, (gdv_int64)v * GDV_MILLIS_IN_DAY, 1, 10, n);
+}
+GDV_DEV gdv_str castVARCHAR_time32_int64(gdv_ctx ctx, gdv_time32 v, gdv_int64 n) { return gdv_dt_text(ctx, v, 2, 12, n); }
+
+// two ASCII digits of v (0..99), first digit in the low byte
+GDV_DEV gdv_uint64 gdv_dt_pair(gdv_int32 v) { return (gdv_uint64)(0x30 + v / 10) | ((gdv_uint64)(0x30 + v % 10) << 8); }
+// the first 24 bytes of the text of a date / timestamp whose year is outside 0..9999 (cold: byte by byte, in registers)
+GDV_DEV void gdv_dt_wide_year(const gdv_ymd& c, gdv_int32 t, gdv_uint64* w0, gdv_uint64* w1, gdv_uint64* w2) {
+  gdv_uint64 a = 0, b = 0, e = 0;
+  gdv_int32 at = 0;
+  auto put = [&](gdv_int64 ch) {
+    const gdv_uint64 x = (gdv_uint64)(ch & 0xFF) << (8 * (at & 7));
+    if (at < 8) a |= x; else if (at < 16) b |= x; else if (at < 24) e |= x;
+    at++;
+  };
+  const gdv_uint64 ay = c.y < 0 ? 0ull - (gdv_uint64)c.y : (gdv_uint64)c.y;
+  if (c.y < 0) put('-');
+  gdv_uint64 p = 1000;
+  while (p * 10 <= ay) p *= 10;
+  for (; p > 0; p /= 10) put('0' + (gdv_int64)(ay / p % 10));
+  auto two = [&](gdv_int64 sep, gdv_int32 v) {
+    put(sep);
+    put('0' + v / 10);
+    put('0' + v % 10);
+  };
+  two('-', c.m);
+  two('-', c.d);
+  two(' ', t / 3600000);
+  two(':', t / 60000 % 60);
+  two(':', t / 1000 % 60);
+  put('.');
+  put('0' + t % 1000 / 100);
+  put('0' + t % 100 / 10);
+  put('0' + t % 10);  // (bytes past the 24th are dropped)
+  *w0 = a;
+  *w1 = b;
+  *w2 = e;
+}
+// bytes [0, len) of the text in w0 | w1 | w2, len <= 24: whole words, the tail as one overlapping word (or 4 + 4 bytes)
+template <typename P>
+GDV_DEV void gdv_dt_store(P dst, gdv_uint64 w0, gdv_uint64 w1, gdv_uint64 w2, gdv_int32 len) {
+  if (len >= 8) {
+    __builtin_memcpy(dst, &w0, 8);
+    gdv_uint64 tail;
+    if (len >= 16) {
+      __builtin_memcpy(dst + 8, &w1, 8);
+      if (len == 16) return;
+      tail = (w1 >> (8 * (len - 16))) | (w2 << (8 * (24 - len)));
+    } else {
+      if (len == 8) return;
+      tail = (w0 >> (8 * (len - 8))) | (w1 << (8 * (16 - len)));
+    }
+    __builtin_memcpy(dst + len - 8, &tail, 8);
+  } else if (len >= 4) {
+    const gdv_uint32 lo = (gdv_uint32)w0, hi = (gdv_uint32)(w0 >> (8 * (len - 4)));
+    __builtin_memcpy(dst, &lo, 4);
+    __builtin_memcpy(dst + len - 4, &hi, 4);
+  } else {
+    gdv_store_low_bytes(dst, w0, len);
+  }
+}
+template <typename P>
+GDV_DEV void gdv_copy_datetime(P dst, const gdv_str& s) {
+  const gdv_int64 v = (gdv_int64)s.lead, days = gdv_floor_div(v, GDV_MILLIS_IN_DAY), r = v % GDV_MILLIS_IN_DAY;
+  const gdv_int32 t = (gdv_int32)(r < 0 ? r + GDV_MILLIS_IN_DAY : r);  // (no days * GDV_MILLIS_IN_DAY: it overflows near INT64_MIN)
+  const gdv_int32 h = t / 3600000, mi = t / 60000 % 60, sec = t / 1000 % 60, f = t % 1000;
+  gdv_uint64 w0, w1, w2 = 0;
+  if (((s.map >> 16) & 3) == 2) {  // hh:mm:ss.sss
+    w0 = gdv_dt_pair(h) | (gdv_uint64)':' << 16 | gdv_dt_pair(mi) << 24 | (gdv_uint64)':' << 40 | gdv_dt_pair(sec) << 48;
+    w1 = (gdv_uint64)'.' | (gdv_uint64)(0x30 + f / 100) << 8 | gdv_dt_pair(f % 100) << 16;
+  } else {
+    const gdv_ymd c = gdv_civil_from_days(days);
+    if (c.y >= 0 && c.y <= 9999) {  // yyyy-MM-dd hh:mm:ss.sss (a date stops after dd)
+      const gdv_int32 y = (gdv_int32)c.y;
+      w0 = gdv_dt_pair(y / 100) | gdv_dt_pair(y % 100) << 16 | (gdv_uint64)'-' << 32 | gdv_dt_pair(c.m) << 40 |
+           (gdv_uint64)'-' << 56;
+      w1 = gdv_dt_pair(c.d) | (gdv_uint64)' ' << 16 | gdv_dt_pair(h) << 24 | (gdv_uint64)':' << 40 | gdv_dt_pair(mi) << 48;
+      w2 = (gdv_uint64)':' | gdv_dt_pair(sec) << 8 | (gdv_uint64)'.' << 24 | (gdv_uint64)(0x30 + f / 100) << 32 |
+           gdv_dt_pair(f % 100) << 40;
+    } else {
+      gdv_dt_wide_year(c, t, &w0, &w1, &w2);
+    }
+  }
+  gdv_dt_store(dst, w0, w1, w2, s.len);
+}
+// the copy entry points of plans that hold a castVARCHAR of a date / time: those values here, everything else as the plan
+// would copy it without them (gdv_str_copy, or gdv_str_copy_ext when it also holds a translate())
+GDV_DEV void gdv_str_copy_dt(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_str_copy(dst, s);
+}
+GDV_DEV void gdv_str_copy_ext_dt(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_str_copy_ext(dst, s);
+}
+
 #ifndef GDV_HOST_BUILD
 // the value the NEXT lane holds (lane 63 gets 0): DPP wave_shl:1, no LDS traffic
 GDV_DEV gdv_uint64 gdv_next_lane(gdv_uint64 v) {
@@ -3339,6 +3666,54 @@ GDV_DEV void gdv_stage_copy_mirh_ext(gdv_lds_u8* dst, const gdv_str& s, const gd
     return;
   }
   gdv_stage_copy_mirh(dst, s, mir, mbase, mlen, bm);
+}
+
+// the staged copies of plans that hold a castVARCHAR of a date / time (gdv_str_copy_dt's counterparts)
+GDV_DEV void gdv_stage_copy_dt(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_dt(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                   gdv_int32 mlen) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_dt(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                    gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh(dst, s, mir, mbase, mlen, bm);
+}
+GDV_DEV void gdv_stage_copy_ext_dt(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy_ext(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_ext_dt(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                       gdv_int32 mlen) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir_ext(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_ext_dt(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase,
+                                        gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_DATETIME) {
+    gdv_copy_datetime(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh_ext(dst, s, mir, mbase, mlen, bm);
 }
 
 // ------------------------------------------------------------------ small-batch filter: scan + emission in the predicate's own workgroup

@@ -517,9 +517,13 @@ class CodeGen {
   bool replace_hits_ = false;      // wave kernels: replace() over a whole column row may be answered by the sweep
   int replace_hook_ = -1;          // ... the hook (match bitmap) that does
   bool translate_ = false;         // a translate() value is copied: the plan's copies take the *_ext entry points
-  // the output copy of a var-len value (the *_ext entry: translate values; only plans that hold one use it)
-  std::string CopyFn() const { return translate_ ? "gdv_str_copy_ext" : "gdv_str_copy"; }
-  std::string StageCopyFn(const std::string& base) const { return translate_ ? base + "_ext" : base; }
+  bool datetime_ = false;          // a castVARCHAR of a date / time is copied: ... the *_dt entry points
+  // the output copy of a var-len value (the *_ext entry: translate values, *_dt: dates and times; only plans that hold one
+  // use it)
+  std::string CopyFn() const { return StageCopyFn("gdv_str_copy"); }
+  std::string StageCopyFn(const std::string& base) const {
+    return base + (translate_ ? "_ext" : "") + (datetime_ ? "_dt" : "");
+  }
   std::ostringstream body_;
   std::map<std::string, std::string> cse_;
   int next_tmp_ = 0;
@@ -710,6 +714,9 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       out->opaque = fn.name() == "reverse" || fn.name() == "replace" || fn.name() == "initcap" || digest ||
                     fn.name() == "repeat" || fn.name() == "space" || fn.name() == "translate" ||
                     (fn.name() == "castVARCHAR" && !args[0].type.is_varlen());
+      if (fn.name() == "castVARCHAR" && (args[0].type.id == kDate32 || args[0].type.id == kDate64 ||
+                                         args[0].type.id == kTimestamp || args[0].type.id == kTime32))
+        datetime_ = true;  // (planned as an ordinary call; its value is a GDV_MAP_DATETIME)
       if ((fn.name() == "upper" || fn.name() == "lower") && args.size() == 1 && args[0].col_slot >= 0) {
         out->col_slot = args[0].col_slot;
         out->col_map = fn.name() == "upper" ? 1 : 2;

@@ -171,6 +171,15 @@ FunctionRegistry::FunctionRegistry() {
   add("castTIMESTAMP", {date64()}, timestamp());
   add("castBIGINT", {date64()}, int64());
   add("castBIGINT", {timestamp()}, int64());
+  // text <-> date / time (milliseconds): parsers that raise on text they do not take; castVARCHAR values are materialised by
+  // the output copy (GDV_MAP_DATETIME).  [recalled semantics: PARITY.md, text <-> date / time]
+  add("castDATE", {utf8()}, date64(), NullPolicy::kNullIfNull, kNeedsContext);
+  add("castTIMESTAMP", {utf8()}, timestamp(), NullPolicy::kNullIfNull, kNeedsContext);
+  add("castTIME", {utf8()}, time32(), NullPolicy::kNullIfNull, kNeedsContext);
+  for (auto& t : {date64(), date32(), timestamp(), time32()})
+    add("castVARCHAR", {t, int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+  add("castTIME", {timestamp()}, time32());
+  add("castTIMESTAMP", {date32()}, timestamp());
 
   // extended math
   for (const char* f : {"cbrt", "exp", "log", "log10", "sqrt", "floor", "ceil", "round",
