@@ -3606,6 +3606,383 @@ GDV_DEV void gdv_str_copy_ext_dt(gdv_uint8* dst, const gdv_str& s) {
   gdv_str_copy_ext(dst, s);
 }
 
+// ------------------------------------------------------------------ hex / unhex / base64 / unbase64 / crc32 over text and binary
+// (to_hex and from_hex are other names of hex and unhex.)  Every function is null if null.
+//   hex(t):      two UPPER-case hex digits per byte, in byte order.  hex(int32 / int64): the two's-complement value as
+//                %X / %lX — upper case, no leading zeros, 0 -> "0".  [letter case and negative integers: recollection]
+//   unhex(text): one byte per two hex digits of either letter case; an odd length or a byte that is not a hex digit
+//                raises GDV_ERR_BAD_ARG.  [raise rather than NULL: recollection]
+//   base64(t):   RFC 4648, standard alphabet, '=' padding, no line breaks.
+//   unbase64(text): the inverse.  The length must be a multiple of 4, every byte an alphabet byte, '=' only in the last one or
+//                two positions (xx==, xxx=); anything else raises.  The unused low bits of the last digit before the padding
+//                are not checked.  [decided here]
+//   crc32(t):    the zlib / IEEE 802.3 CRC-32 (reflected 0xEDB88320, initial value and final XOR 0xFFFFFFFF) of the bytes, as a
+//                non-negative int64; crc32("") = 0.  [widened to int64: recollection]
+// The four var-len results are values of one kind, GDV_MAP_ENCODE, which is NOT one of GDV_MAP_SPECIAL: only plans that hold
+// one copy their outputs through the *_enc entry points below.  p / lim / flags & GDV_STR_INBUF / map & GDV_MAP_CASE describe
+// the SOURCE view, `lead` is its length, `len` the length of the result and (map >> 16) & 7 the sub-kind.  The length of a
+// result follows from the source's length alone (unbase64: and from its last two bytes, the padding), so the functions read
+// no byte of the text; the copy reads the source 8 bytes at a time through its case map, converts the word in registers
+// (SWAR) and stores whole words plus one overlapping tail word.  The decoders validate the words they convert and raise
+// there, once per row, through the error word kept in `lead_p`.
+#define GDV_MAP_ENCODE 32768
+#define GDV_ENC_HEX 0
+#define GDV_ENC_UNHEX 1
+#define GDV_ENC_BASE64 2
+#define GDV_ENC_UNBASE64 3
+#define GDV_ENC_HEXINT 4  // `lead` is the integer itself
+
+GDV_DEV gdv_str gdv_enc_value(const gdv_str& s, gdv_int64 len, gdv_int32 sub) {
+  gdv_str r = s;
+  r.lead = (gdv_uint64)(s.len > 0 ? s.len : 0);
+  r.lead_p = nullptr;
+  r.len = (gdv_int32)len;
+  r.flags = s.flags & GDV_STR_INBUF;
+  r.map = GDV_MAP_ENCODE | (sub << 16) | (s.map & GDV_MAP_CASE);
+  return r;
+}
+// the result lengths (INT32_MAX bytes at most: longer results raise, as repeat's do)
+GDV_DEV gdv_str hex_utf8(gdv_ctx ctx, gdv_str s) {
+  if (s.len <= 0) return gdv_empty_str();
+  if (s.len > 0x3fffffff) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return gdv_empty_str();
+  }
+  return gdv_enc_value(s, 2ll * s.len, GDV_ENC_HEX);
+}
+GDV_DEV gdv_str hex_binary(gdv_ctx ctx, gdv_str s) { return hex_utf8(ctx, s); }
+GDV_DEV gdv_str base64_utf8(gdv_ctx ctx, gdv_str s) {
+  if (s.len <= 0) return gdv_empty_str();
+  const gdv_int64 len = ((gdv_int64)s.len + 2) / 3 * 4;
+  if (len > 0x7fffffffll) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return gdv_empty_str();
+  }
+  return gdv_enc_value(s, len, GDV_ENC_BASE64);
+}
+GDV_DEV gdv_str base64_binary(gdv_ctx ctx, gdv_str s) { return base64_utf8(ctx, s); }
+GDV_DEV gdv_str unhex_utf8(gdv_ctx ctx, gdv_str s) {
+  if (s.len <= 0) return gdv_empty_str();
+  if (s.len & 1) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return gdv_empty_str();
+  }
+  gdv_str r = gdv_enc_value(s, s.len / 2, GDV_ENC_UNHEX);
+  r.lead_p = (const gdv_uint8*)ctx.err;
+  return r;
+}
+GDV_DEV gdv_str unbase64_utf8(gdv_ctx ctx, gdv_str s) {
+  if (s.len <= 0) return gdv_empty_str();
+  if (s.len & 3) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return gdv_empty_str();
+  }
+  // the padding: the row's last two bytes, out of its last word
+  const gdv_uint32 last2 = (gdv_uint32)(s.len >= 8 ? gdv_raw_word_at(s, s.len - 8) >> 48 : gdv_raw_word_at(s, 0) >> (8 * (s.len - 2))) & 0xffffu;
+  const gdv_int32 pad = (last2 >> 8) != '=' ? 0 : (last2 & 0xffu) != '=' ? 1 : 2;
+  gdv_str r = gdv_enc_value(s, s.len / 4 * 3 - pad, GDV_ENC_UNBASE64);  // (at least one byte)
+  r.lead_p = (const gdv_uint8*)ctx.err;
+  return r;
+}
+// hex of an integer: `bits` = 32 or 64, the width whose two's complement is printed
+GDV_DEV gdv_str gdv_enc_hex_int(gdv_uint64 v, gdv_int32 bits) {
+  gdv_str r = gdv_empty_str();
+  if (bits == 32) v &= 0xffffffffull;
+  r.lead = v;
+  r.len = v == 0 ? 1 : (67 - __builtin_clzll(v)) / 4;
+  r.flags = 0;
+  r.map = GDV_MAP_ENCODE | (GDV_ENC_HEXINT << 16);
+  return r;
+}
+GDV_DEV gdv_str hex_int32(gdv_ctx ctx, gdv_int32 v) { return gdv_enc_hex_int((gdv_uint64)(gdv_uint32)v, 32); }
+GDV_DEV gdv_str hex_int64(gdv_ctx ctx, gdv_int64 v) { return gdv_enc_hex_int((gdv_uint64)v, 64); }
+
+// ---- the word conversions
+// bytes b0..b3 of x as eight upper-case hex digits, b0's high digit in the low byte (the nibble spread, then gdv_hex8's
+// digit / letter select with 'A' - '9' - 1 = 7 in place of 39)
+GDV_DEV gdv_uint64 gdv_enc_hex4(gdv_uint32 x) {
+  gdv_uint64 t = x;
+  t = (t | (t << 16)) & 0x0000ffff0000ffffull;
+  t = (t | (t << 8)) & 0x00ff00ff00ff00ffull;  // one source byte per 16 bits
+  const gdv_uint64 v = ((t >> 4) & 0x000f000f000f000full) | ((t & 0x000f000f000f000full) << 8);
+  const gdv_uint64 letter = ((v + 0x0606060606060606ull) >> 4) & 0x0101010101010101ull;  // 1 where the nibble is 10..15
+  return v + 0x3030303030303030ull + letter * 7ull;
+}
+// gdv_hex8 in upper case: eight hex digits of x, most significant first
+GDV_DEV gdv_uint64 gdv_hex8_upper(gdv_uint32 x) { return gdv_enc_hex4(__builtin_bswap32(x)); }
+// 1 in every byte of h (all bytes < 0x80) that lies in [lo, hi]: a = 0x80 - lo, b = 0x7f - hi in every byte
+GDV_DEV gdv_uint64 gdv_enc_range(gdv_uint64 h, gdv_uint64 a, gdv_uint64 b) { return (((h + a) & ~(h + b)) >> 7) & 0x0101010101010101ull; }
+// the 4 bytes the eight hex digits of w spell; *bad becomes non-zero when a byte of w is not a hex digit
+GDV_DEV gdv_uint32 gdv_enc_unhex8(gdv_uint64 w, gdv_uint64* bad) {
+  const gdv_uint64 h = w & GDV_B7F, one = 0x0101010101010101ull;
+  const gdv_uint64 digit = gdv_enc_range(h, 0x5050505050505050ull, 0x4646464646464646ull);                              // '0'..'9'
+  const gdv_uint64 letter = gdv_enc_range(h & 0x5f5f5f5f5f5f5f5full, 0x3f3f3f3f3f3f3f3full, 0x3939393939393939ull);  // 'A'..'F', 'a'..'f'
+  *bad |= ((digit | letter) ^ one) | ((w >> 7) & one);
+  const gdv_uint64 n = (h & 0x0f0f0f0f0f0f0f0full) + letter * 9ull;
+  gdv_uint64 p = ((n << 4) | (n >> 8)) & 0x00ff00ff00ff00ffull;  // one result byte per 16 bits
+  p = (p | (p >> 8)) & 0x0000ffff0000ffffull;
+  return (gdv_uint32)(p | (p >> 16));
+}
+// the four sextets of the bytes b0 b1 b2 (the low three bytes of x), the first in the low byte
+GDV_DEV gdv_uint32 gdv_enc_sextets(gdv_uint32 x) {
+  const gdv_uint32 t = __builtin_bswap32(x) >> 8;  // b0 << 16 | b1 << 8 | b2
+  return ((t >> 18) & 0x3fu) | ((t >> 4) & 0x3f00u) | ((t << 10) & 0x3f0000u) | ((t << 24) & 0x3f000000u);
+}
+// eight sextets (one per byte) -> their alphabet bytes: 'A' + s, + 6 from 26 ('a'), - 75 from 52 ('0'), - 15 at 62 ('+'),
+// + 3 at 63 ('/') — range compares on the word, no table
+GDV_DEV gdv_uint64 gdv_enc_b64_chars(gdv_uint64 s) {
+  const gdv_uint64 one = 0x0101010101010101ull;
+  const gdv_uint64 ge26 = ((s + 0x6666666666666666ull) >> 7) & one, ge52 = ((s + 0x4c4c4c4c4c4c4c4cull) >> 7) & one;
+  const gdv_uint64 ge62 = ((s + 0x4242424242424242ull) >> 7) & one, ge63 = ((s + 0x4141414141414141ull) >> 7) & one;
+  return s + 0x4141414141414141ull + ge26 * 6ull + ge63 * 3ull - ge52 * 75ull - ge62 * 15ull;
+}
+// the eight alphabet bytes of the 6 source bytes in the low 48 bits of w
+GDV_DEV gdv_uint64 gdv_enc_b64_word(gdv_uint64 w) {
+  return gdv_enc_b64_chars((gdv_uint64)gdv_enc_sextets((gdv_uint32)w) | (gdv_uint64)gdv_enc_sextets((gdv_uint32)(w >> 24)) << 32);
+}
+// the 6 bytes (low 48 bits) the eight alphabet bytes of w spell; *bad becomes non-zero when a byte is outside the alphabet
+GDV_DEV gdv_uint64 gdv_enc_unb64_word(gdv_uint64 w, gdv_uint64* bad) {
+  const gdv_uint64 h = w & GDV_B7F, one = 0x0101010101010101ull;
+  const gdv_uint64 up = gdv_enc_range(h, 0x3f3f3f3f3f3f3f3full, 0x2525252525252525ull);     // 'A'..'Z' -> 0..25
+  const gdv_uint64 low = gdv_enc_range(h, 0x1f1f1f1f1f1f1f1full, 0x0505050505050505ull);    // 'a'..'z' -> 26..51
+  const gdv_uint64 dig = gdv_enc_range(h, 0x5050505050505050ull, 0x4646464646464646ull);    // '0'..'9' -> 52..61
+  const gdv_uint64 plus = gdv_enc_range(h, 0x5555555555555555ull, 0x5454545454545454ull);   // '+' -> 62
+  const gdv_uint64 slash = gdv_enc_range(h, 0x5151515151515151ull, 0x5050505050505050ull);  // '/' -> 63
+  *bad |= ((up | low | dig | plus | slash) ^ one) | ((w >> 7) & one);
+  const gdv_uint64 s = (h + dig * 4ull + plus * 19ull + slash * 16ull - up * 65ull - low * 71ull) & 0x3f3f3f3f3f3f3f3full;
+  const gdv_uint32 a = (gdv_uint32)s, b = (gdv_uint32)(s >> 32);
+  const gdv_uint32 na = (a & 0x3fu) << 18 | (a & 0x3f00u) << 4 | (a & 0x3f0000u) >> 10 | a >> 24;  // s0 << 18 | s1 << 12 | s2 << 6 | s3
+  const gdv_uint32 nb = (b & 0x3fu) << 18 | (b & 0x3f00u) << 4 | (b & 0x3f0000u) >> 10 | b >> 24;
+  return (gdv_uint64)(__builtin_bswap32(na) >> 8) | (gdv_uint64)(__builtin_bswap32(nb) >> 8) << 24;
+}
+// bytes [0, len) of w, len in 1..8: one word, two overlapping half words, or the 2 + 1 ladder
+template <typename P>
+GDV_DEV void gdv_enc_store_short(P dst, gdv_uint64 w, gdv_int32 len) {
+  if (len >= 8) {
+    __builtin_memcpy(dst, &w, 8);
+  } else if (len >= 4) {
+    const gdv_uint32 lo = (gdv_uint32)w, hi = (gdv_uint32)(w >> (8 * (len - 4)));
+    __builtin_memcpy(dst, &lo, 4);
+    __builtin_memcpy(dst + len - 4, &hi, 4);
+  } else {
+    gdv_store_low_bytes(dst, w, len);
+  }
+}
+// A result written as a stream of words: `acc` holds the `n` (0..7) bytes not stored yet, `last` the word stored before
+// them, `at` the bytes stored.  gdv_enc_put appends the low k (1..8) bytes of w (the bytes above them are zero);
+// gdv_enc_finish stores the rest as one word that overlaps the last one (a result below 8 bytes: gdv_enc_store_short).
+template <typename P>
+GDV_DEV void gdv_enc_put(P dst, gdv_uint64& acc, gdv_uint64& last, gdv_int32& n, gdv_int32& at, gdv_uint64 w, gdv_int32 k) {
+  acc |= w << (8 * n);
+  if (n + k >= 8) {
+    __builtin_memcpy(dst + at, &acc, 8);
+    last = acc;
+    at += 8;
+    acc = n > 0 ? w >> (8 * (8 - n)) : 0ull;
+    n += k - 8;
+  } else {
+    n += k;
+  }
+}
+template <typename P>
+GDV_DEV void gdv_enc_finish(P dst, gdv_uint64 acc, gdv_uint64 last, gdv_int32 n, gdv_int32 at) {
+  if (n == 0) return;
+  if (at > 0) {
+    const gdv_uint64 tail = (last >> (8 * n)) | (acc << (8 * (8 - n)));
+    __builtin_memcpy(dst + at + n - 8, &tail, 8);
+  } else {
+    gdv_enc_store_short(dst, acc, n);
+  }
+}
+// the source view of an encode value, read through its case map
+GDV_DEV gdv_str gdv_enc_source(const gdv_str& s) {
+  gdv_str src = s;
+  src.len = (gdv_int32)s.lead;
+  src.map = s.map & GDV_MAP_CASE;
+  src.flags = s.flags & GDV_STR_INBUF;
+  return src;
+}
+template <typename P>
+GDV_DEV void gdv_copy_hex(P dst, const gdv_str& s) {
+  const gdv_str src = gdv_enc_source(s);
+  const gdv_int32 n = src.len;
+  gdv_int32 i = 0;
+  for (; i + 8 <= n; i += 8) {
+    const gdv_uint64 w = gdv_word_at(src, i);
+    const gdv_uint64 a = gdv_enc_hex4((gdv_uint32)w), b = gdv_enc_hex4((gdv_uint32)(w >> 32));
+    __builtin_memcpy(dst + 2 * i, &a, 8);
+    __builtin_memcpy(dst + 2 * i + 8, &b, 8);
+  }
+  if (n - i >= 4) {
+    const gdv_uint64 a = gdv_enc_hex4((gdv_uint32)gdv_word_at(src, i));
+    __builtin_memcpy(dst + 2 * i, &a, 8);
+    i += 4;
+  }
+  if (i == n) return;
+  if (n >= 4) {  // the last four source bytes again: one word that overlaps what is written
+    const gdv_uint64 a = gdv_enc_hex4((gdv_uint32)gdv_word_at(src, n - 4));
+    __builtin_memcpy(dst + 2 * n - 8, &a, 8);
+  } else {
+    gdv_enc_store_short(dst, gdv_enc_hex4((gdv_uint32)gdv_word_at(src, 0)), 2 * n);
+  }
+}
+template <typename P>
+GDV_DEV void gdv_copy_hex_int(P dst, const gdv_str& s) {
+  const gdv_uint64 w0 = gdv_hex8_upper((gdv_uint32)(s.lead >> 32)), w1 = gdv_hex8_upper((gdv_uint32)s.lead);
+  const gdv_int32 skip = 16 - s.len;  // leading zeros that are not printed
+  gdv_uint64 o0, o1 = 0;
+  if (skip >= 8) {
+    o0 = w1 >> (8 * (skip - 8));
+  } else if (skip > 0) {
+    o0 = (w0 >> (8 * skip)) | (w1 << (8 * (8 - skip)));
+    o1 = w1 >> (8 * skip);
+  } else {
+    o0 = w0;
+    o1 = w1;
+  }
+  gdv_dt_store(dst, o0, o1, 0ull, s.len);
+}
+template <typename P>
+GDV_DEV void gdv_copy_unhex(P dst, const gdv_str& s) {
+  const gdv_str src = gdv_enc_source(s);
+  const gdv_int32 n = src.len, out = s.len;  // n = 2 * out
+  gdv_uint64 bad = 0;
+  gdv_int32 i = 0;
+  for (; i + 16 <= n; i += 16) {
+    const gdv_uint64 w = (gdv_uint64)gdv_enc_unhex8(gdv_word_at(src, i), &bad) | (gdv_uint64)gdv_enc_unhex8(gdv_word_at(src, i + 8), &bad) << 32;
+    __builtin_memcpy(dst + i / 2, &w, 8);
+  }
+  if (i < n) {
+    if (n >= 16) {  // the last sixteen digits again: one word that overlaps what is written
+      const gdv_uint64 w = (gdv_uint64)gdv_enc_unhex8(gdv_word_at(src, n - 16), &bad) | (gdv_uint64)gdv_enc_unhex8(gdv_word_at(src, n - 8), &bad) << 32;
+      __builtin_memcpy(dst + out - 8, &w, 8);
+    } else {  // 2..14 digits: the bytes past them read as '0'
+      const gdv_uint64 zeros = 0x3030303030303030ull;
+      const gdv_uint64 m0 = gdv_low_bytes_mask(n), m1 = gdv_low_bytes_mask(n > 8 ? n - 8 : 0);
+      const gdv_uint64 w0 = (gdv_word_at(src, 0) & m0) | (zeros & ~m0);
+      const gdv_uint64 w1 = n > 8 ? (gdv_word_at(src, 8) & m1) | (zeros & ~m1) : zeros;
+      gdv_enc_store_short(dst, (gdv_uint64)gdv_enc_unhex8(w0, &bad) | (gdv_uint64)gdv_enc_unhex8(w1, &bad) << 32, out);
+    }
+  }
+  if (bad != 0) gdv_raise_bits((gdv_uint32*)s.lead_p, GDV_ERR_BAD_ARG);
+}
+template <typename P>
+GDV_DEV void gdv_copy_base64(P dst, const gdv_str& s) {
+  const gdv_str src = gdv_enc_source(s);
+  const gdv_int32 n = src.len;
+  gdv_int32 i = 0, o = 0;
+  for (; i + 6 <= n; i += 6, o += 8) {  // (the word's last two bytes belong to the next step)
+    const gdv_uint64 c = gdv_enc_b64_word(gdv_word_at(src, i));
+    __builtin_memcpy(dst + o, &c, 8);
+  }
+  const gdv_int32 r = n - i;  // 0..5 bytes left: 4 or 8 more bytes of text, '=' where a sextet has no source byte
+  if (r == 0) return;
+  gdv_uint64 c = gdv_enc_b64_word(gdv_word_at(src, i) & gdv_low_bytes_mask(r));
+  const gdv_uint64 eq = 0x3d3d3d3d3d3d3d3dull;
+  const gdv_int32 keep = r + 1 + (r > 3 ? 1 : 0);  // alphabet bytes: 2, 3, 4, 6, 7
+  if (r != 3) c = (c & gdv_low_bytes_mask(keep)) | (eq & ~gdv_low_bytes_mask(keep));
+  if (r > 3) {
+    __builtin_memcpy(dst + o, &c, 8);
+  } else {
+    const gdv_uint32 c4 = (gdv_uint32)c;
+    __builtin_memcpy(dst + o, &c4, 4);
+  }
+}
+template <typename P>
+GDV_DEV void gdv_copy_unbase64(P dst, const gdv_str& s) {
+  const gdv_str src = gdv_enc_source(s);
+  const gdv_int32 n = src.len, out = s.len, pad = n / 4 * 3 - out;  // n is a multiple of 4, pad 0..2
+  gdv_uint64 bad = 0, acc = 0, last = 0;
+  gdv_int32 fill = 0, at = 0;
+  for (gdv_int32 i = 0; i < n; i += 8) {
+    // the characters of this step: 8, or the text's last 4; the one or two '=' that end the text, like the bytes past it,
+    // count as 'A'
+    const gdv_int32 nc = (n - i < 8 ? 4 : 8) - (i + 8 >= n ? pad : 0);
+    const gdv_uint64 w = (gdv_word_at(src, i) & gdv_low_bytes_mask(nc)) | (0x4141414141414141ull & ~gdv_low_bytes_mask(nc));
+    const gdv_uint64 b = gdv_enc_unb64_word(w, &bad);
+    const gdv_int32 k = out - (i / 8 * 6) < 6 ? out - (i / 8 * 6) : 6;  // result bytes of this step
+    gdv_enc_put(dst, acc, last, fill, at, b & gdv_low_bytes_mask(k), k);
+  }
+  gdv_enc_finish(dst, acc, last, fill, at);
+  if (bad != 0) gdv_raise_bits((gdv_uint32*)s.lead_p, GDV_ERR_BAD_ARG);
+}
+template <typename P>
+GDV_DEV void gdv_copy_encode(P dst, const gdv_str& s) {
+  const gdv_int32 sub = (s.map >> 16) & 7;
+  if (sub == GDV_ENC_HEX) gdv_copy_hex(dst, s);
+  else if (sub == GDV_ENC_BASE64) gdv_copy_base64(dst, s);
+  else if (sub == GDV_ENC_UNHEX) gdv_copy_unhex(dst, s);
+  else if (sub == GDV_ENC_UNBASE64) gdv_copy_unbase64(dst, s);
+  else gdv_copy_hex_int(dst, s);
+}
+
+// ---- crc32: slice-by-8 — eight table reads and seven XORs per 8 source bytes, the tail's r < 8 bytes with r reads.  The
+// tables (8 KiB) are computed when the kernel is compiled and sit in its constant data.
+struct gdv_crc32_tables {
+  gdv_uint32 t[8][256];
+  constexpr gdv_crc32_tables() : t() {
+    for (gdv_uint32 i = 0; i < 256; i++) {
+      gdv_uint32 c = i;
+      for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+      t[0][i] = c;
+    }
+    for (int k = 1; k < 8; k++)
+      for (gdv_uint32 i = 0; i < 256; i++) t[k][i] = t[0][t[k - 1][i] & 0xffu] ^ (t[k - 1][i] >> 8);
+  }
+};
+GDV_DEV gdv_int64 gdv_crc32_buf(const gdv_str& s) {
+  static constexpr gdv_crc32_tables T{};
+  gdv_uint32 crc = 0xffffffffu;
+  gdv_int32 i = 0;
+  for (; i + 8 <= s.len; i += 8) {
+    const gdv_uint64 x = gdv_word_at(s, i) ^ (gdv_uint64)crc;
+    crc = T.t[7][x & 0xff] ^ T.t[6][(x >> 8) & 0xff] ^ T.t[5][(x >> 16) & 0xff] ^ T.t[4][(x >> 24) & 0xff] ^
+          T.t[3][(x >> 32) & 0xff] ^ T.t[2][(x >> 40) & 0xff] ^ T.t[1][(x >> 48) & 0xff] ^ T.t[0][x >> 56];
+  }
+  const gdv_int32 r = s.len - i;
+  if (r > 0) {  // byte j of the last r: table r - 1 - j; the state's bytes past them move down
+    const gdv_uint64 x = (gdv_word_at(s, i) & gdv_low_bytes_mask(r)) ^ (gdv_uint64)crc;
+    crc = r < 4 ? crc >> (8 * r) : 0u;
+#pragma unroll
+    for (int j = 0; j < 7; j++)
+      if (j < r) crc ^= T.t[(r - 1 - j) & 7][(x >> (8 * j)) & 0xff];
+  }
+  return (gdv_int64)(crc ^ 0xffffffffu);
+}
+GDV_DEV gdv_int64 crc32_utf8(gdv_str s) { return gdv_crc32_buf(s); }
+GDV_DEV gdv_int64 crc32_binary(gdv_str s) { return gdv_crc32_buf(s); }
+
+// the copy entry points of plans that hold an encode value: those values here, everything else as the plan would copy it
+// without them
+GDV_DEV void gdv_str_copy_enc(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_str_copy(dst, s);
+}
+GDV_DEV void gdv_str_copy_ext_enc(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_str_copy_ext(dst, s);
+}
+GDV_DEV void gdv_str_copy_dt_enc(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_str_copy_dt(dst, s);
+}
+GDV_DEV void gdv_str_copy_ext_dt_enc(gdv_uint8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_str_copy_ext_dt(dst, s);
+}
+
 #ifndef GDV_HOST_BUILD
 // the value the NEXT lane holds (lane 63 gets 0): DPP wave_shl:1, no LDS traffic
 GDV_DEV gdv_uint64 gdv_next_lane(gdv_uint64 v) {
@@ -3714,6 +4091,92 @@ GDV_DEV void gdv_stage_copy_mirh_ext_dt(gdv_lds_u8* dst, const gdv_str& s, const
     return;
   }
   gdv_stage_copy_mirh_ext(dst, s, mir, mbase, mlen, bm);
+}
+
+// the staged copies of plans that hold an encode value (gdv_str_copy_enc's counterparts)
+GDV_DEV void gdv_stage_copy_enc(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh(dst, s, mir, mbase, mlen, bm);
+}
+GDV_DEV void gdv_stage_copy_ext_enc(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_ext(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_ext_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir_ext(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_ext_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh_ext(dst, s, mir, mbase, mlen, bm);
+}
+GDV_DEV void gdv_stage_copy_dt_enc(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_dt(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_dt_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir_dt(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_dt_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh_dt(dst, s, mir, mbase, mlen, bm);
+}
+GDV_DEV void gdv_stage_copy_ext_dt_enc(gdv_lds_u8* dst, const gdv_str& s) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_ext_dt(dst, s);
+}
+GDV_DEV void gdv_stage_copy_mir_ext_dt_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mir_ext_dt(dst, s, mir, mbase, mlen);
+}
+GDV_DEV void gdv_stage_copy_mirh_ext_dt_enc(gdv_lds_u8* dst, const gdv_str& s, const gdv_lds_u8* mir, const gdv_uint8* mbase, gdv_int32 mlen, const gdv_uint64* bm) {
+  if (s.map & GDV_MAP_ENCODE) {
+    gdv_copy_encode(dst, s);
+    return;
+  }
+  gdv_stage_copy_mirh_ext_dt(dst, s, mir, mbase, mlen, bm);
 }
 
 // ------------------------------------------------------------------ small-batch filter: scan + emission in the predicate's own workgroup

@@ -518,11 +518,12 @@ class CodeGen {
   int replace_hook_ = -1;          // ... the hook (match bitmap) that does
   bool translate_ = false;         // a translate() value is copied: the plan's copies take the *_ext entry points
   bool datetime_ = false;          // a castVARCHAR of a date / time is copied: ... the *_dt entry points
-  // the output copy of a var-len value (the *_ext entry: translate values, *_dt: dates and times; only plans that hold one
-  // use it)
+  bool encode_ = false;            // a hex / unhex / base64 / unbase64 value is copied: ... the *_enc entry points
+  // the output copy of a var-len value (the *_ext entry: translate values, *_dt: dates and times, *_enc: hex / base64 and
+  // their inverses; only plans that hold one use it)
   std::string CopyFn() const { return StageCopyFn("gdv_str_copy"); }
   std::string StageCopyFn(const std::string& base) const {
-    return base + (translate_ ? "_ext" : "") + (datetime_ ? "_dt" : "");
+    return base + (translate_ ? "_ext" : "") + (datetime_ ? "_dt" : "") + (encode_ ? "_enc" : "");
   }
   std::ostringstream body_;
   std::map<std::string, std::string> cse_;
@@ -605,6 +606,12 @@ void TranslateTable(const std::string& from, const std::string& to, std::string*
     bytes += e.second;
   }
   *tab += bytes;
+}
+
+// hex / unhex / base64 / unbase64 (and their other names): values of the kind GDV_MAP_ENCODE, materialised by the output copy
+bool IsEncodeFunction(const std::string& name) {
+  static const std::set<std::string> k = {"hex", "to_hex", "unhex", "from_hex", "base64", "unbase64"};
+  return k.count(name) != 0;
 }
 
 // functions whose fast path is "the string is pure ASCII" (character index == byte index)
@@ -714,6 +721,7 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       out->opaque = fn.name() == "reverse" || fn.name() == "replace" || fn.name() == "initcap" || digest ||
                     fn.name() == "repeat" || fn.name() == "space" || fn.name() == "translate" ||
                     (fn.name() == "castVARCHAR" && !args[0].type.is_varlen());
+      if (IsEncodeFunction(fn.name())) out->opaque = encode_ = true;  // (planned as an ordinary call; its value is a GDV_MAP_ENCODE)
       if (fn.name() == "castVARCHAR" && (args[0].type.id == kDate32 || args[0].type.id == kDate64 ||
                                          args[0].type.id == kTimestamp || args[0].type.id == kTime32))
         datetime_ = true;  // (planned as an ordinary call; its value is a GDV_MAP_DATETIME)
@@ -2594,6 +2602,7 @@ bool ByteFree(const Node& n) {
       "substr", "substring", "left", "right", "upper", "lower", "octet_length", "bit_length", "char_length",
       "length", "lengthUtf8", "castVARCHAR", "concat", "concatOperator", "reverse", "initcap", "lpad", "rpad", "isnull", "hashSHA256", "sha256",
       "hashSHA1", "sha1", "sha", "hashMD5", "md5", "repeat",
+      "hex", "to_hex", "unhex", "from_hex", "base64",  // (unbase64 reads the row's last word for the padding)
       "isnotnull"};
   switch (n.kind()) {
     case NodeKind::kField:
@@ -3536,7 +3545,7 @@ bool MaterialisesBytes(const Node& n) {
   const std::string& f = fn.name();
   if (f == "concat" || f == "concatOperator" || f == "lpad" || f == "rpad" || f == "reverse" || f == "replace" || f == "initcap" ||
       f == "hashSHA256" || f == "sha256" || f == "hashSHA1" || f == "sha1" || f == "sha" || f == "hashMD5" || f == "md5" ||
-      f == "repeat" || f == "space" || f == "translate")
+      f == "repeat" || f == "space" || f == "translate" || IsEncodeFunction(f))
     return true;
   return f == "castVARCHAR" && !fn.children().empty() && !fn.children()[0]->return_type().is_varlen();
 }

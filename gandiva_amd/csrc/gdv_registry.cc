@@ -361,6 +361,19 @@ FunctionRegistry::FunctionRegistry() {
   add("space", {int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
   add("translate", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext,
       "gdv_translate");  // planned by gdv_planner.cc
+  // bytes <-> printable text and checksums: hex / to_hex, unhex / from_hex, base64, unbase64 are values the output copy
+  // materialises (GDV_MAP_ENCODE; the decoders raise on text they do not take), crc32 is the zlib CRC-32 widened to int64.
+  // [RFC 4648 / zlib pin the bytes; letter case, raising and the widening are recalled: PARITY.md, hex / base64 / crc32]
+  for (const char* f : {"hex", "to_hex"})
+    for (auto& t : {utf8(), binary(), int32(), int64()})
+      add(f, {t}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext, Sym("hex", {t}));
+  for (const char* f : {"unhex", "from_hex"})
+    add(f, {utf8()}, binary(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext, "unhex_utf8");
+  for (auto& t : {utf8(), binary()}) {
+    add("base64", {t}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
+    add("crc32", {t}, int64());
+  }
+  add("unbase64", {utf8()}, binary(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
   add("locate", {utf8(), utf8()}, int32(), NullPolicy::kNullIfNull, kNeedsContext);
   add("locate", {utf8(), utf8(), int32()}, int32(), NullPolicy::kNullIfNull, kNeedsContext);
   add("position", {utf8(), utf8()}, int32(), NullPolicy::kNullIfNull, kNeedsContext, Sym("locate", {utf8(), utf8()}));
