@@ -4,7 +4,7 @@
 // reference's `precompiled/*.cc` bitcode library and
 // `BitMapAccumulator` / `bitmap.cc` helpers (rows 8, 13).  It is embedded verbatim in
 // libgandiva_amd.so and handed to the runtime compiler together with the kernel body the
-// planner emits for one Projector / Filter (gdv_planner.cc).  Function names follow the
+// planner emits for one Projector / Filter (gdv_planner.cc and its units).  Function names follow the
 // reference's `<name>_<type>_<type>` convention so a plan dump reads like the
 // reference's IR.  Everything is written for 64-wide wavefronts: one wavefront handles
 // 64 consecutive rows per sub-tile, i.e. exactly one 64-bit Arrow validity word
@@ -2837,7 +2837,7 @@ GDV_DEV gdv_str rtrim_utf8(gdv_str s) {
 }
 GDV_DEV gdv_str btrim_utf8(gdv_str s) { return rtrim_utf8(ltrim_utf8(s)); }
 
-// SQL LIKE.  The pattern is compiled at Make time (gdv_planner.cc) into parallel arrays in
+// SQL LIKE.  The pattern is compiled at Make time (gdv_codegen_functions.cc, CompileLike) into parallel arrays in
 // constant memory: kind[i] = 0 literal byte, 1 '_' (exactly one UTF-8 character),
 // 2 '%' (any run, possibly empty); byte[i] = the literal.  Matching is the classic
 // two-cursor wildcard walk with a single backtrack point (the last '%'): O(len * plen) worst

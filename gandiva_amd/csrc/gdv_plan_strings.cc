@@ -1,0 +1,997 @@
+#include "gdv_planner_internal.h"
+
+#include <algorithm>
+#include <cstring>
+#include <regex>
+
+namespace gdv::planner {
+
+namespace {
+
+// ---- pieces of the string skeletons shared by the scanner shape and the wave shape
+// pointers of the tile function: var-len / fixed-width inputs, outputs, the selection vector
+void EmitStringPointersAndLoads(std::ostringstream& s, CodeGen& cg, KernelPlan* plan, bool with_outputs,
+                                bool wave_shape = false) {
+  const bool sel = cg.selection();
+  const int nin = plan->layout.n_in;
+  for (int k = 0; k < nin; k++) {
+    const DataType& t = cg.schema_[plan->input_fields[k]].type;
+    if (t.is_varlen() && cg.needs_values_[k]) {
+      s << "  const gdv_uint8* __restrict__ sd" << k << " = (const gdv_uint8*)A.in[" << k << "].data;\n"
+        << "  const gdv_int32* __restrict__ so" << k << " = A.in[" << k << "].offsets;\n"
+        << "  const gdv_uint8* slim" << k << " = sd" << k << " + A.in[" << k << "].bits.nwords;\n";
+    } else if (t.id != kBool && cg.needs_values_[k]) {
+      s << "  const " << t.CType() << "* __restrict__ in" << k << " = (const " << t.CType() << "*)A.in[" << k
+        << "].data;\n";
+    }
+  }
+  for (size_t e = 0; with_outputs && e < plan->output_types.size(); e++) {
+    const DataType& t = plan->output_types[e];
+    if (t.is_varlen()) {
+      s << "  gdv_uint8* __restrict__ outd" << e << " = (gdv_uint8*)A.out[" << e << "].data;\n"
+        << "  gdv_int32* __restrict__ outo" << e << " = A.out[" << e << "].offsets;\n";
+    } else if (t.id != kBool) {
+      s << "  " << t.CType() << "* __restrict__ out" << e << " = (" << t.CType() << "*)A.out[" << e << "].data;\n";
+    }
+  }
+  if (sel)
+    s << "  const " << SelCType(cg.sel_mode_) << "* __restrict__ selv = (const " << SelCType(cg.sel_mode_)
+      << "*)A.sel;\n";
+
+  // ---- loads: offsets, fixed-width values, validity / bool words
+  s << "  // ---- loads of this wave's GDV_U sub-tiles, issued back to back\n";
+  if (sel) s << "  gdv_int64 srow[GDV_U];\n";
+  for (int k = 0; k < nin; k++) {
+    const DataType& t = cg.schema_[plan->input_fields[k]].type;
+    if (t.id == kBool) {
+      if (cg.needs_values_[k]) {
+        if (sel) s << "  bool x" << k << "[GDV_U];\n";
+        else s << "  const gdv_uint64 dw" << k << " = gdv_bitmap_tile(A.in[" << k << "].bits, wbase, lane, GDV_U);\n";
+      }
+    } else if (t.is_varlen()) {
+      if (cg.needs_values_[k]) {
+        // (wave shape: only the start offsets are loaded; a row's end is the next lane's start)
+        // (... of a CONTIGUOUS run of rows: under a selection vector both ends are gathered)
+        if (wave_shape && !sel) s << "  gdv_int32 oa" << k << "[GDV_U];\n";
+        else s << "  gdv_int32 oa" << k << "[GDV_U], ob" << k << "[GDV_U];\n";
+      }
+    } else if (cg.needs_values_[k]) {
+      s << "  " << t.CType() << " c" << k << "[GDV_U];\n";
+    }
+    if (cg.needs_validity_[k]) {
+      if (sel) s << "  bool b" << k << "[GDV_U];\n";
+      else s << "  const gdv_uint64 vw" << k << " = gdv_bitmap_tile(A.in[" << k << "].valid, wbase, lane, GDV_U);\n";
+    }
+  }
+  s << "#pragma unroll\n  for (int u = 0; u < GDV_U; u++) {\n"
+    << "    const gdv_int64 row = rbase + u * 64 + lane;\n"
+    << "    const bool live = row < n;\n"
+    << "    (void)live;\n";
+  if (sel) {
+    EmitSelectionLoads(s, cg, plan);
+  } else {
+    for (int k = 0; k < nin; k++) {
+      const DataType& t = cg.schema_[plan->input_fields[k]].type;
+      if (t.is_varlen()) {
+        // rows past the end take the closing offset: length 0, and the span stays contiguous
+        if (cg.needs_values_[k] && wave_shape)
+          s << "    oa" << k << "[u] = so" << k << "[live ? row : n];\n";
+        else if (cg.needs_values_[k])
+          s << "    oa" << k << "[u] = so" << k << "[live ? row : n]; ob" << k << "[u] = so" << k
+            << "[row + 1 < n ? row + 1 : n];\n";
+      } else if (t.id != kBool && cg.needs_values_[k]) {
+        s << "    c" << k << "[u] = live ? " << (plan->opts.nt_loads ? "gdv_ldnt" : "gdv_ld") << "(in" << k
+          << ", row) : (" << t.CType() << ")0;\n";
+      }
+    }
+  }
+  s << "  }\n";
+
+}
+
+// the rolled row loop: prologue (this sub-tile's inputs picked at index 0), the fused body, rotation
+// of the per-sub-tile registers; the caller appends its own rotations and closes the loop ("  }\n")
+void EmitStringRowLoop(std::ostringstream& s, CodeGen& cg, KernelPlan* plan, bool wave_shape = false,
+                       const std::string& at_top = std::string()) {
+  const bool sel = cg.selection();
+  const int nin = plan->layout.n_in;
+  // The row loop is NOT unrolled: the per-sub-tile registers are read and written through
+  // gdv_pick / gdv_put (selects on the wave-uniform u), so the fused body exists once — a
+  // quarter of the code, the compile time and the VGPRs of the unrolled form.
+  s << "GDV_ROW_LOOP\n  for (int u = 0; u < GDV_U; u++) {\n"
+    << at_top
+    << "    {\n"
+    << "      const gdv_int64 row = rbase + u * 64 + lane;\n"
+    << "      const bool live = row < n;\n"
+    << "      const gdv_uint64 livemask = __ballot(live);\n"
+    << "      (void)livemask; (void)row;\n";
+  for (int k = 0; k < nin; k++) {
+    const DataType& t = cg.schema_[plan->input_fields[k]].type;
+    if (t.id == kBool) {
+      if (cg.needs_values_[k] && sel) s << "      const bool x" << k << "_u = x" << k << "[0];\n";
+    } else if (t.is_varlen()) {
+      if (cg.needs_values_[k] && wave_shape && !sel)
+        s << "      const gdv_int32 oa" << k << "_u = oa" << k << "[0];\n"
+          << "      const gdv_int32 ob" << k << "_u = gdv_next_lane_i32(oa" << k << "_u, u + 1 < GDV_U ? __builtin_amdgcn_readfirstlane(oa"
+          << k << "[GDV_U > 1 ? 1 : 0]) : sp1" << k << ", lane);\n";
+      else if (cg.needs_values_[k])
+        s << "      const gdv_int32 oa" << k << "_u = oa" << k << "[0], ob" << k << "_u = ob" << k << "[0];\n";
+      if (cg.needs_values_[k] && cg.row_ascii_slots_.count(k))
+        // exact variant: ASCII is a fact about THIS row (conservatively: about the 16-byte pieces it touches)
+        s << "      const gdv_str s" << k << " = gdv_with_lead(gdv_make_str(sd" << k << ", oa" << k << "_u, ob" << k << "_u, slim" << k
+          << ", sfl" << k << "), hi8_" << k << ", hm_ok" << k << ", cb" << k << ", oa" << k << "_u - sb" << k << ");\n";
+      else if (cg.needs_values_[k])
+        s << "      const gdv_str s" << k << " = gdv_make_str(sd" << k << ", oa" << k << "_u, ob" << k << "_u, slim" << k
+          << ", sfl" << k << ");\n";
+      if (cg.needs_values_[k] && cg.sel_ascii_check_ && cg.ascii_slots_.count(k))
+        s << "      nasc" << k << " |= __ballot(live && !gdv_row_is_ascii(s" << k << "));\n";
+    } else if (cg.needs_values_[k]) {
+      s << "      const " << t.CType() << " c" << k << "_u = c" << k << "[0];\n";
+    }
+    if (cg.needs_validity_[k] && sel) s << "      const bool b" << k << "_u = b" << k << "[0];\n";
+  }
+  if (!sel) EmitTileWords(s, cg, plan);
+  {
+    // the body addresses per-sub-tile inputs as NAME[u]: here they are the NAME_u picked above
+    static const std::regex per_u("\\b(oa|ob|c|x|b)([0-9]+)\\[u\\]");
+    s << std::regex_replace(cg.body_.str(), per_u, "$1$2_u");
+  }
+  s << "    }\n    // next sub-tile to the front\n";
+  for (int k = 0; k < nin; k++) {
+    const DataType& t = cg.schema_[plan->input_fields[k]].type;
+    if (t.id == kBool) {
+      if (cg.needs_values_[k] && sel) s << "    gdv_rot(x" << k << ");\n";
+    } else if (t.is_varlen()) {
+      if (cg.needs_values_[k]) s << "    gdv_rot(oa" << k << ");" << (wave_shape && !sel ? "" : " gdv_rot(ob" + std::to_string(k) + ");") << "\n";
+    } else if (cg.needs_values_[k]) {
+      s << "    gdv_rot(c" << k << ");\n";
+    }
+    if (cg.needs_validity_[k] && sel) s << "    gdv_rot(b" << k << ");\n";
+  }
+}
+
+// What the byte sweep of one var-len input has to produce; one entry per var-len input whose bytes the plan reads.
+struct SweepInputs {
+  int k;                                // the input slot ...
+  std::string K;                        // ... and its number as text
+  std::vector<int> hooks;               // '%needle%' match bitmaps over this column
+  bool want_ascii;                      // some function consults the ASCII flag of its views
+  std::vector<const VarlenOut*> flats;  // outputs that are this column's (mapped) bytes
+  bool nothing() const { return hooks.empty() && !want_ascii && flats.empty(); }
+};
+std::vector<SweepInputs> SweepInputsOf(CodeGen& cg, KernelPlan* plan) {
+  std::vector<SweepInputs> all;
+  for (int k = 0; k < plan->layout.n_in; k++) {
+    if (!(cg.schema_[plan->input_fields[k]].type.is_varlen() && cg.needs_values_[k])) continue;
+    SweepInputs in{k, std::to_string(k), {}, cg.ascii_slots_.count(k) != 0, {}};
+    for (size_t h = 0; h < cg.contains_hooks_.size(); h++)
+      if (cg.contains_hooks_[h].slot == k) in.hooks.push_back(static_cast<int>(h));
+    for (auto& vo : cg.varlen_outs_)
+      if (vo.flat_slot == k) in.flats.push_back(&vo);
+    all.push_back(in);
+  }
+  return all;
+}
+
+// the needle's bytes inside the 8-byte word the matcher compares
+uint64_t NeedleMask(const ContainsHook& hk) { return hk.needle.size() >= 8 ? ~0ull : ((1ull << (8 * hk.needle.size())) - 1); }
+
+// Before the sweep: every hook's match bitmap and the '%needle%' as the matcher's three constants.  Wave-shaped kernels
+// (round 4) carry them in the kernel TEXT: the needle is a literal of the plan, and as immediates its bytes cost no
+// scalar loads, no registers across the row loop and let the compiler fold the first-byte splats (the
+// round-3 verdict priced the runtime needle among the 0.2 ms the generic emitter paid over its
+// prototype).  Plans that differ in the needle are different kernels there; the scanner shape keeps the
+// needle a run-time constant (one code object for every pattern of a given length).
+void EmitHookPreamble(std::ostream& s, CodeGen& cg, const std::vector<int>& hooks) {
+  for (int h : hooks) {
+    const ContainsHook& hk = cg.contains_hooks_[h];
+    const uint64_t mask = NeedleMask(hk);
+    const std::string H = std::to_string(h);
+    s << "  gdv_uint64* const hit" << h << " = lds_hit + " << h << " * GDV_HIT_WORDS;\n";
+    if (cg.bake_needles_) {
+      uint64_t v = 0;
+      std::memcpy(&v, hk.needle.data(), std::min<size_t>(8, hk.needle.size()));
+      v &= mask;
+      s << "  const gdv_uint64 nd" << H << " = " << Hex64(v) << ";  // the needle: a literal of the plan\n"
+        << "  const gdv_uint32 ns0_" << H << " = " << Hex64((v & 0xff) * 0x01010101ull) << ", ns1_" << H << " = "
+        << Hex64(((v >> 8) & 0xff) * 0x01010101ull) << ";\n";
+    } else {
+      s << "  const gdv_uint64 nd" << H << " = gdv_load8_raw(" << cg.hook_tables_[h] << ") & " << Hex64(mask)
+        << ";  // the needle: a runtime constant\n"
+        << "  const gdv_uint32 ns0_" << H << " = (gdv_uint32)(nd" << H << " & 0xffull) * 0x01010101u, ns1_" << H << " = (gdv_uint32)((nd" << H
+        << " >> 8) & 0xffull) * 0x01010101u;\n";
+    }
+  }
+}
+
+// One step of the sweep, per hook: the lane's 16 bytes w[0..1] (and the 8 behind them: the next lane's, `tail` for lane 63)
+// against the needle -> 16 match bits into the hook's bitmap.  `bound`: the end of the span being swept.
+void EmitMatchStep(std::ostream& s, const std::string& ind, CodeGen& cg, const SweepInputs& in, const std::string& bound) {
+  for (int h : in.hooks) {
+    const ContainsHook& hk = cg.contains_hooks_[h];
+    const std::string H = std::to_string(h), M = std::to_string(hk.map), mask = Hex64(NeedleMask(hk));
+    s << ind << "{\n"
+      << ind << "  const gdv_uint64 lo = gdv_map8(w[0], " << M << "), hi = gdv_map8(w[1], " << M << ");\n"
+      << ind << "  gdv_uint64 nx = gdv_next_lane(lo);\n"
+      << ind << "  if (lane == 63) nx = gdv_map8(tail, " << M << ");\n"
+      << ind << "  const gdv_uint32 m = " << (tl_ablation ? "(GDV_ABL & 1) ? (gdv_uint32)(lo >> 60) : " : "") << "gdv_match8(lo, hi, nd" << H << ", " << mask << ", ns0_" << H << ", ns1_" << H << ") |\n"
+      << ind << "                       (gdv_match8(hi, nx, nd" << H << ", " << mask << ", ns0_" << H << ", ns1_" << H << ") << 8);\n"
+      << ind << "  if (hm_ok" << in.K << " && a < " << bound << ") ((gdv_uint16*)hit" << H << ")[(a - sb" << in.K << ") >> 4] = (gdv_uint16)m;\n"
+      << ind << "}\n";
+  }
+}
+
+// the flag of a column's views where it is not what a sweep found: optimistic ASCII where a function consults it (the
+// pre-pass computed the lengths under it; a compile-time fact for the row bodies: every general UTF-8 path folds away)
+void EmitTileFlag(std::ostream& s, const SweepInputs& in) {
+  s << "  const gdv_int32 sfl" << in.K << " = inb" << in.K << (in.want_ascii ? " | GDV_STR_ASCII" : "") << ";\n";
+}
+
+// Wave shape: the wave tile's span.  Its ends come from two scalar loads (the sweep does not wait for the offsets' vector
+// loads); one wave-uniform range test per tile makes every 8-byte read of these rows unchecked.  False: nothing to sweep.
+bool EmitWaveSpanHeader(std::ostream& s, const SweepInputs& in) {
+  const std::string& K = in.K;
+  s << "  const gdv_int32 sp0" << K << " = so" << K << "[rbase];\n"
+    << "  const gdv_int32 sp1" << K << " = so" << K << "[last_tile ? n : rbase + 64 * GDV_U];\n"
+    << "  const gdv_int32 inb" << K << " = sd" << K << " + sp1" << K << " + 8 <= slim" << K << " ? GDV_STR_INBUF : 0;\n";
+  if (!in.flats.empty())
+    s << "  const gdv_int32 so0_" << K << " = so" << K << "[0];  // the batch's first offset (flat outputs rebase by it)\n";
+  if (in.nothing()) EmitTileFlag(s, in);
+  return !in.nothing();
+}
+
+// byte sweep of every var-len input (scanner shape): tile-wide ASCII flag, '%needle%' match
+// bitmaps, flat outputs.  (Wave-shaped kernels sweep one sub-tile at a time: EmitWaveSweep.)
+void EmitStringSweep(std::ostringstream& s, CodeGen& cg, KernelPlan* plan) {
+  const bool sel = cg.selection();
+  // ---- sweep: lanes over the bytes of each var-len input's span
+  for (const SweepInputs& in : SweepInputsOf(cg, plan)) {
+    const auto& [k, K, hooks, want_ascii, flats] = in;
+    if (sel) {
+      s << "  const gdv_int32 sfl" << K << " = 0;\n";
+      continue;
+    }
+    // one wave-uniform range test per tile makes every 8-byte read of these rows unchecked
+    s << "  const gdv_int32 inb" << K << " = sd" << K << " + __builtin_amdgcn_readlane(ob" << K
+      << "[GDV_U - 1], 63) + 8 <= slim" << K << " ? GDV_STR_INBUF : 0;\n";
+    if (!flats.empty())
+      s << "  const gdv_int32 so0_" << K << " = so" << K << "[0];  // the batch's first offset (flat outputs rebase by it)\n";
+    if (hooks.empty() && !want_ascii && flats.empty()) {
+      s << "  const gdv_int32 sfl" << K << " = inb" << K << ";\n";
+      continue;
+    }
+    s << "  // ---- byte sweep of input " << k << ": the wave tile's rows are one contiguous span\n"
+      << "  const gdv_int32 sp0" << K << " = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+      << "  const gdv_int32 sp1" << K << " = __builtin_amdgcn_readlane(ob" << K << "[GDV_U - 1], 63);\n"
+      << "  const gdv_int32 sb" << K << " = sp0" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + sp0" << K << ") & 15);\n"
+      << "  const bool hm_ok" << K << " = sp1" << K << " - sb" << K << " <= GDV_SPAN_MAX;\n"
+      << "  (void)hm_ok" << K << ";\n"
+      << "  gdv_uint64 sacc" << K << " = 0;\n";
+    EmitHookPreamble(s, cg, hooks);
+    s << "  for (gdv_int32 c = sb" << K << "; c < " << AblSel(64, "sb" + K, "sp1" + K) << "; c += 1024) {\n"
+      << "    const gdv_int32 a = c + 16 * lane;\n"
+      << "    gdv_uint64 w[2] = {0ull, 0ull};\n"
+      << "    if (a < sp1" << K << ") __builtin_memcpy(w, __builtin_assume_aligned(sd" << K << " + a, 16), 16);\n"
+      << "    sacc" << K << " |= w[0] | w[1];\n";
+    if (!hooks.empty())
+      s << "    gdv_uint64 tail = 0;  // lane 63's halo: the first 8 bytes of the next step\n"
+        << "    if (lane == 63 && a + 16 < sp1" << K << ") tail = gdv_load8_raw(sd" << K << " + a + 16);\n";
+    EmitMatchStep(s, "    ", cg, in, "sp1" + K);
+    s << "  }\n";
+    // optimistic flat outputs: their place in the output is known from the input offsets alone, so
+    // the span is copied right here, while the sweep's lines are still in L2 / L1.  (Moving the copy
+    // behind the post of the tile totals, "into the shadow" of the scanner hand-off, measured
+    // slower: 1.90 vs 1.78 ms, same box, profiles/r02_c5_tuning.txt.)
+    for (auto* vo : flats)
+      s << "  if (" << AblNot(8) << "optflat && (gdv_int64)sp1" << K << " - so0_" << K << " <= A.out[" << vo->e << "].cap)\n"
+        << "    gdv_flat_copy(outd" << vo->e << " + (sp0" << K << " - so0_" << K << "), sd" << K << " + sp0" << K << ", sp1" << K
+        << " - sp0" << K << ", " << vo->flat_map << ", lane);\n";
+    if (want_ascii)
+      s << "  const gdv_int32 sfl" << K << " = inb" << K << " | (__ballot((sacc" << K
+        << " & GDV_B80) != 0) == 0 ? GDV_STR_ASCII : 0);\n";
+    else
+      s << "  const gdv_int32 sfl" << K << " = inb" << K << ";\n";
+    if (!hooks.empty()) s << "  __builtin_amdgcn_wave_barrier();\n";
+  }
+}
+
+// Exact variant, kernels that have no other reason to read column K's bytes (a ByteFree pre-pass):
+// a bare sweep of the wave tile's span — 16 B per lane and step, OR-reduced — gives the tile's ASCII flag.
+// Needs sp0K / sp1K (the span) and sdK / slimK in scope; defines sflK.
+std::string ExactAsciiTileFlag(const std::string& K) {
+  std::ostringstream s;
+  s << "  gdv_uint64 sacc" << K << " = 0;\n"
+    << "  for (gdv_int32 c = sp0" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + sp0" << K << ") & 15); c < sp1" << K << "; c += 1024) {\n"
+    << "    const gdv_int32 a = c + 16 * lane;\n"
+    << "    gdv_uint64 w[2] = {0ull, 0ull};\n"
+    << "    if (a < sp1" << K << ") __builtin_memcpy(w, __builtin_assume_aligned(sd" << K << " + a, 16), 16);\n"
+    << "    sacc" << K << " |= w[0] | w[1];\n"
+    << "  }\n"
+    << "  const gdv_int32 sfl" << K << " = (sd" << K << " + sp1" << K << " + 8 <= slim" << K << " ? GDV_STR_INBUF : 0) |\n"
+    << "                       (__ballot((sacc" << K << " & GDV_B80) != 0) == 0 ? GDV_STR_ASCII : 0);\n";
+  return s.str();
+}
+
+// The byte sweep of wave-shaped kernels, one SUB-TILE (64 rows) at a time, at the top of the row
+// loop: lanes over the bytes of the sub-tile's span — 16 B per lane and step, coalesced, the first
+// step of the NEXT sub-tile already in flight while this one's rows are evaluated.  Per piece:
+//   * tile-wide ASCII check (optimistic: the row bodies were compiled for ASCII; a byte >= 0x80
+//     raises NOTASCII after the loop and the host re-runs the batch on the general kernel),
+//   * '%needle%' match bits -> LDS bitmap of the sub-tile's span,
+//   * flat outputs leave straight from the registers (a piece is stored by the sub-tile that holds
+//     its last byte's predecessor: pieces that straddle two sub-tiles are stored exactly once),
+//   * the bytes themselves -> the LDS MIRROR of the span, which the rows' staged copies read.
+// Why per sub-tile and not per wave tile as in the first wave-shaped kernels: by the time the rows
+// of a 512-row tile re-read their bytes (8-byte loads at the row's offset) the lines had left the
+// XCD's L2 — 0.6 GB of extra fabric reads on C5, 1.40 x the algorithmic traffic
+// (profiles/r03_c5_traffic.txt).  A sub-tile's span is small enough to keep in LDS (GDV_SUB_SPAN =
+// 32 bytes per row; longer spans — wave-uniform — read HBM as before), so nothing is read twice.
+struct WaveSweepText {
+  std::string prologue;   // before the row loop
+  std::string per_sub;    // top of the row loop's body (u = the sub-tile)
+  std::string epilogue;   // after the row loop
+};
+// sg (round 6): sub-tiles whose spans ONE sweep covers (GDV_SG; 1 = one sub-tile at a time, rounds 3-5).  A 64-row span of
+// 12-byte rows fills three quarters of a 1024-byte step; four of them fill three steps exactly.
+void EmitWaveSweep(CodeGen& cg, KernelPlan* plan, int mirror_slot, bool prepass, WaveSweepText* out, int sg = 1) {
+  std::ostringstream s, b, e;
+  const bool grouped = sg > 1;
+  const std::string SG = std::to_string(sg);
+  for (const SweepInputs& in : SweepInputsOf(cg, plan)) {
+    const auto& [k, K, hooks, want_ascii, flats] = in;
+    const bool mirror = mirror_slot == k && !prepass;  // (a pre-pass needs the match bits only)
+    if (prepass && mirror_slot != k) {
+      // a pre-pass sweeps nothing but the column whose replace() counts matches in the bitmap; views
+      // carry the flags the main kernel will give them (the optimistic ASCII flag where consulted)
+      s << "  const gdv_int32 sp1" << K << " = so" << K << "[last_tile ? n : rbase + 64 * GDV_U];\n";
+      if (want_ascii && cg.exact_ascii_) {
+        s << "  const gdv_int32 sp0" << K << " = so" << K << "[rbase];\n" << ExactAsciiTileFlag(K);
+      } else {
+        s << "  const gdv_int32 sfl" << K << " = (sd" << K << " + sp1" << K << " + 8 <= slim" << K << " ? GDV_STR_INBUF : 0)"
+          << (want_ascii ? " | GDV_STR_ASCII" : "") << ";\n";
+      }
+      continue;
+    }
+    if (!EmitWaveSpanHeader(s, in)) continue;
+    s << "  // ---- byte sweep of input " << k << ", one sub-tile at a time (inside the row loop)\n"
+      << "  gdv_uint64 sacc" << K << " = 0;\n";
+    EmitHookPreamble(s, cg, hooks);
+    if (mirror)
+      s << "  gdv_lds_u8* const mir" << K << " = (gdv_lds_u8*)lds_in;  // LDS mirror of the current sub-tile's span\n";
+    // the first piece of sub-tile 0 (every later sub-tile's first piece is loaded one iteration ahead)
+    s << "  gdv_uint64 wn" << K << "[2] = {0ull, 0ull};\n"
+      << (hooks.empty() ? "" : "  gdv_uint64 tn" + K + " = 0;  // lane 63's halo (the 8 bytes behind its piece), loaded WITH the piece\n")
+      << "  {\n"
+      << "    const gdv_int32 e0 = GDV_U > " << SG << " ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > " << SG << " ? " << SG << " : 0]) : sp1" << K << ";\n"
+      << "    const gdv_int32 b0 = sp0" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + sp0" << K << ") & 15);\n"
+      << "    if (" << AblNot(64) << "b0 + 16 * lane < e0) __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K
+      << " + b0 + 16 * lane, 16), 16);\n"
+      << (hooks.empty() ? "" : "    if (" + AblNot(64) + "lane == 63 && b0 + 1024 < e0) tn" + K + " = gdv_load8_raw(sd" + K + " + b0 + 1024);\n")
+      << "  }\n";
+    // the two ragged ends of the tile's span (whole 16-byte pieces that overlap their neighbours)
+    for (auto* vo : flats)
+      s << "  const gdv_int32 fcap" << vo->e << " = (gdv_int32)(A.out[" << vo->e << "].cap > 0x7fffffff ? 0x7fffffff : A.out[" << vo->e
+        << "].cap);\n";
+    for (auto* vo : flats)
+      s << "  " << AblIf(8) << "gdv_sweep_edges(outd" << vo->e << ", sd" << K << ", sp0" << K << ", sp1" << K << ", so0_" << K
+        << ", " << vo->flat_map << ", A.out[" << vo->e << "].cap, lane);\n";
+    if (want_ascii && cg.exact_ascii_)
+      // exact variant: the flag of the CURRENT sub-tile, set by its sweep at the top of the row loop
+      s << "  const gdv_int32 sfl" << K << " = inb" << K << ";  // (the rows' views take a per-row flag: gdv_row_has_high)\n"
+        << "  gdv_uint64 sawhi" << K << " = 0;  // OR of every byte swept so far (reported as SAWUTF8)\n"
+        << "  bool hi8_" << K << " = false;  // the current sub-tile's span holds a byte >= 0x80\n"
+        << "  gdv_uint64* const cb" << K << " = lds_hit + " << cg.CbIndex(k) << " * GDV_HIT_WORDS;  // continuation-byte bitmap of the sub-tile's span\n";
+    else
+      EmitTileFlag(s, in);
+
+    // ---- per sub-tile
+    if (grouped) {
+      // the span of a GROUP of GDV_SG sub-tiles, swept when its first sub-tile comes up; ssK / seK / sbK / hm_okK stay what
+      // they are for the group's other sub-tiles (the rows address the mirror and the bitmaps relative to sbK)
+      s << "  gdv_int32 ss" << K << " = 0, se" << K << " = 0, sb" << K << " = 0;\n"
+        << "  bool hm_ok" << K << " = false;\n"
+        << "  (void)ss" << K << "; (void)hm_ok" << K << ";\n";
+      b << "    // byte sweep of the span of this group of " << SG << " sub-tiles of input " << k << " (every " << SG << "th iteration)\n"
+        << "    if ((u & (" << SG << " - 1)) == 0) {\n"
+        << "    ss" << K << " = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+        << "    se" << K << " = u + " << SG << " < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > " << SG << " ? " << SG << " : 0]) : sp1" << K << ";\n"
+        << "    sb" << K << " = ss" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + ss" << K << ") & 15);\n"
+        << "    hm_ok" << K << " = se" << K << " - sb" << K << " <= GDV_SUB_SPAN;  // wave-uniform: the span fits the LDS bitmap / mirror\n";
+    } else {
+      b << "    // byte sweep of this sub-tile's span of input " << k << "\n"
+        << "    const gdv_int32 ss" << K << " = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+        << "    const gdv_int32 se" << K << " = u + 1 < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > 1 ? 1 : 0]) : sp1" << K << ";\n"
+        << "    const gdv_int32 sb" << K << " = ss" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + ss" << K << ") & 15);\n"
+        << "    const bool hm_ok" << K << " = se" << K << " - sb" << K << " <= GDV_SUB_SPAN;  // wave-uniform: the span fits the LDS bitmap / mirror\n"
+        << "    (void)hm_ok" << K << ";\n";
+    }
+    b << "    for (gdv_int32 c = sb" << K << "; c < " << AblSel(64, "sb" + K, "se" + K) << "; c += 1024) {\n"
+      << "      const gdv_int32 a = c + 16 * lane;\n"
+      << "      const gdv_uint64 w[2] = {wn" << K << "[0], wn" << K << "[1]};\n"
+      << "      wn" << K << "[0] = 0ull; wn" << K << "[1] = 0ull;\n"
+      << (hooks.empty() ? "" : "      const gdv_uint64 tail = tn" + K + ";  // (lane 63 only) — loaded one step ahead like the piece: nothing here waits for a load it has just issued\n"
+                               "      tn" + K + " = 0ull;\n")
+      << "      if (a + 1024 < se" << K << ") __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + a + 1024, 16), 16);\n"
+      << (hooks.empty() ? "" : "      if (lane == 63 && a + 1024 + 16 < se" + K + ") tn" + K + " = gdv_load8_raw(sd" + K + " + a + 1024 + 16);\n")
+      << "      sacc" << K << " |= w[0] | w[1];\n";
+    if (want_ascii && cg.exact_ascii_) {
+      cg.row_ascii_slots_.insert(k);
+      b << "      { const gdv_uint64 hbw = __ballot(((w[0] | w[1]) & GDV_B80) != 0);\n"
+        << "        const gdv_uint32 cm = hbw != 0 ? gdv_cont_mask16(w[0], w[1]) : 0u;  // (wave-uniform branch: ASCII steps skip the packing)\n"
+        << "        if (hm_ok" << K << " && a < se" << K << ") ((gdv_uint16*)cb" << K << ")[(a - sb" << K << ") >> 4] = (gdv_uint16)cm; }\n";
+    }
+    EmitMatchStep(b, "      ", cg, in, "se" + K);
+    if (mirror)
+      b << "      if (hm_ok" << K << " && a < se" << K << ") __builtin_memcpy(mir" << K << " + (a - sb" << K << "), w, 16);\n";
+    // a piece is stored by the sub-tile in whose span it ENDS (a + 16 <= se): the piece that
+    // straddles two sub-tiles is the next one's first piece; the tile's own ends: gdv_sweep_edges
+    for (auto* vo : flats)
+      b << "      " << AblIf(8) << "gdv_sweep_store32(outd" << vo->e << ", a - so0_" << K
+        << ", w, " << vo->flat_map << ", a >= sp0" << K << " && a + 16 <= se" << K << ", fcap" << vo->e << ");\n";
+    const std::string SG2 = std::to_string(2 * sg);
+    b << "    }\n"
+      << "    if (u + " << SG << " < GDV_U) {  // the first piece of the next " << (grouped ? "group's" : "sub-tile's") << " span\n"
+      << "      const gdv_int32 e2 = u + " << SG2 << " < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > " << SG2 << " ? " << SG2 << " : 0]) : sp1" << K << ";\n"
+      << "      const gdv_int32 nb = se" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + se" << K << ") & 15);\n"
+      << "      if (" << AblNot(64) << "nb + 16 * lane < e2) __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K
+      << " + nb + 16 * lane, 16), 16);\n"
+      << (hooks.empty() ? "" : "      if (" + AblNot(64) + "lane == 63 && nb + 1024 < e2) tn" + K + " = gdv_load8_raw(sd" + K + " + nb + 1024);\n")
+      << "    }\n";
+    if (want_ascii && cg.exact_ascii_)
+      // (the sweep of a sub-tile covers whole 16-byte pieces: a few bytes of the neighbouring rows may
+      // clear the flag needlessly — the general paths are exact for ASCII rows too)
+      b << "    hi8_" << K << " = __ballot((sacc" << K << " & GDV_B80) != 0) != 0;  // this sub-tile's span holds a byte >= 0x80\n"
+        << "    sawhi" << K << " |= sacc" << K << ";\n"
+        << "    sacc" << K << " = 0;\n";
+    if (!hooks.empty() || mirror || (want_ascii && cg.exact_ascii_)) b << "    __builtin_amdgcn_wave_barrier();\n";
+    if (grouped) b << "    }  // (group's first sub-tile)\n";
+
+    // ---- after the loop
+    if (want_ascii && cg.exact_ascii_ && !prepass)
+      e << "  if (__ballot((sawhi" << K << " & GDV_B80) != 0) != 0 && lane == 0) gdv_raise_bits(A.err, GDV_ERR_SAWUTF8);\n";
+    else if (want_ascii && !prepass)  // (the main kernel raises it)
+      e << "  if (__ballot((sacc" << K << " & GDV_B80) != 0) != 0 && lane == 0) gdv_raise_bits(A.err, GDV_ERR_NOTASCII);\n";
+  }
+  out->prologue = s.str();
+  out->per_sub = b.str();
+  out->epilogue = e.str();
+}
+
+// The byte sweep of wave-shaped kernels WITHOUT an LDS mirror: the whole wave tile's span in one
+// go, before the row loop (full 1024-byte steps: cheaper per byte than the per-sub-tile sweep,
+// whose steps are three quarters full on average).  Taken when no staged copy would read the
+// mirror — flat-only plans, outputs that are not readable views (reverse, replace, digits).
+void EmitWaveTileSweep(std::ostringstream& s, CodeGen& cg, KernelPlan* plan, std::string* epilogue) {
+  std::ostringstream e;
+  for (const SweepInputs& in : SweepInputsOf(cg, plan)) {
+    const auto& [k, K, hooks, want_ascii, flats] = in;
+    if (cg.selection()) {
+      // selected rows are not one span of bytes: nothing to sweep, no tile-wide fact about them — every row
+      // function takes its general (UTF-8-exact, range-checked) path, as in the scanner-shaped kernel
+      // ... except the OPTIMISTIC one the pre-pass made: a function that consults the ASCII flag gets it set here too
+      // (so both kernels compute the same lengths) and every row, which reads its bytes in this kernel anyway, checks it
+      if (want_ascii) {
+        s << "  const gdv_int32 sfl" << K << " = GDV_STR_ASCII;\n"
+          << "  gdv_uint64 nasc" << K << " = 0;  // rows that turned out to hold a byte >= 0x80\n";
+        e << "  if (nasc" << K << " != 0 && lane == 0) gdv_raise_bits(A.err, GDV_ERR_NOTASCII);\n";
+      } else {
+        s << "  const gdv_int32 sfl" << K << " = 0;\n";
+      }
+      continue;
+    }
+    if (!EmitWaveSpanHeader(s, in)) continue;
+    s << "  // ---- byte sweep of input " << k << ": the wave tile's rows are one contiguous span\n"
+      << "  const gdv_int32 sb" << K << " = sp0" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + sp0" << K << ") & 15);\n"
+      << "  const bool hm_ok" << K << " = sp1" << K << " - sb" << K << " <= GDV_SPAN_MAX;\n"
+      << "  (void)hm_ok" << K << ";\n"
+      << "  gdv_uint64 sacc" << K << " = 0;\n";
+    EmitHookPreamble(s, cg, hooks);
+    for (auto* vo : flats)
+      s << "  const gdv_int32 fcap" << vo->e << " = (gdv_int32)(A.out[" << vo->e << "].cap > 0x7fffffff ? 0x7fffffff : A.out[" << vo->e
+        << "].cap);\n";
+    // software-pipelined: the next step's 16 bytes — and lane 63's halo, the 8 bytes behind its
+    // piece — are in flight while this step's are matched / stored
+    s << "  gdv_uint64 wn" << K << "[2] = {0ull, 0ull};\n"
+      << (hooks.empty() ? "" : "  gdv_uint64 tn" + K + " = 0;\n")
+      << "  if (sb" << K << " + 16 * lane < sp1" << K << ") __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + sb" << K << " + 16 * lane, 16), 16);\n"
+      << (hooks.empty() ? "" : "  if (lane == 63 && sb" + K + " + 1024 < sp1" + K + ") tn" + K + " = gdv_load8_raw(sd" + K + " + sb" + K + " + 1024);\n")
+      << "  for (gdv_int32 c = sb" << K << "; c < " << AblSel(64, "sb" + K, "sp1" + K) << "; c += 1024) {\n"
+      << "    const gdv_int32 a = c + 16 * lane;\n"
+      << "    const gdv_uint64 w[2] = {wn" << K << "[0], wn" << K << "[1]};\n"
+      << "    wn" << K << "[0] = 0ull; wn" << K << "[1] = 0ull;\n"
+      << (hooks.empty() ? "" : "    const gdv_uint64 tail = tn" + K + ";  // (lane 63 only)\n    tn" + K + " = 0ull;\n")
+      << "    if (a + 1024 < sp1" << K << ") __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + a + 1024, 16), 16);\n"
+      << (hooks.empty() ? "" : "    if (lane == 63 && a + 1024 + 16 < sp1" + K + ") tn" + K + " = gdv_load8_raw(sd" + K + " + a + 1024 + 16);\n")
+      << "    sacc" << K << " |= w[0] | w[1];\n";
+    EmitMatchStep(s, "    ", cg, in, "sp1" + K);
+    // flat outputs leave straight from the sweep's registers; a piece's bytes outside this wave's
+    // span [sp0, sp1) belong to the neighbouring tiles
+    for (auto* vo : flats)
+      s << "    " << AblIf(8) << "gdv_sweep_store32(outd" << vo->e << ", a - so0_" << K
+        << ", w, " << vo->flat_map << ", a >= sp0" << K << " && a + 16 <= sp1" << K << ", fcap" << vo->e << ");\n";
+    s << "  }\n";
+    for (auto* vo : flats)
+      s << "  " << AblIf(8) << "gdv_sweep_edges(outd" << vo->e << ", sd" << K << ", sp0" << K << ", sp1" << K << ", so0_" << K
+        << ", " << vo->flat_map << ", A.out[" << vo->e << "].cap, lane);\n";
+    if (want_ascii && cg.exact_ascii_) {
+      // exact variant: the tile's flag is what its sweep found
+      s << "  const bool hi8_" << K << " = __ballot((sacc" << K << " & GDV_B80) != 0) != 0;\n"
+        << "  const gdv_int32 sfl" << K << " = inb" << K << " | (hi8_" << K << " ? 0 : GDV_STR_ASCII);\n";
+      e << "  if (hi8_" << K << " && lane == 0) gdv_raise_bits(A.err, GDV_ERR_SAWUTF8);\n";
+    } else {
+      // (a tile that breaks the optimistic flag raises NOTASCII: the host re-runs the batch on the exact variant of these kernels)
+      EmitTileFlag(s, in);
+      if (want_ascii) e << "  if (__ballot((sacc" << K << " & GDV_B80) != 0) != 0 && lane == 0) gdv_raise_bits(A.err, GDV_ERR_NOTASCII);\n";
+    }
+    if (!hooks.empty()) s << "  __builtin_amdgcn_wave_barrier();\n";
+  }
+  *epilogue = e.str();
+}
+
+const char* const kStringKernelOpen =
+    "#ifndef GDV_STRING_KERNEL_ATTR\n#define GDV_STRING_KERNEL_ATTR\n#endif\n"
+    "extern \"C\" __global__ void GDV_STRING_KERNEL_ATTR __launch_bounds__(GDV_WAVES * 64) GDV_KERNEL_NAME(const gdv_args A) {\n"
+    "  const int lane = threadIdx.x & 63;\n"
+    "  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));\n";
+
+// what every string plan records of its generation
+void BindStringPlan(CodeGen& cg, KernelPlan* plan) {
+  BindInputs(cg, plan);
+  plan->string_skeleton = true;
+  for (size_t k = 0; k < plan->input_fields.size(); k++)
+    plan->has_varlen_input |= cg.schema_[plan->input_fields[k]].type.is_varlen() && cg.needs_values_[k];
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ string plans
+// Kernels that read or write var-len columns use their own skeleton (round 2):
+//   tile     one workgroup = GDV_WAVES waves x GDV_U sub-tiles x 64 rows; a wave's rows occupy ONE
+//            contiguous span of each var-len input's data buffer
+//   sweep    lanes over the BYTES of that span: tile-wide ASCII flag, '%needle%' match bitmaps
+//   rows     lane = row: the fused expression bodies; var-len results are kept as views
+//   offsets  per-wave DPP scan of the lengths -> workgroup totals -> ONE granule posted to the
+//            scanner wave (workgroup 0), ONE granule polled for the tile's exclusive prefix
+//   bytes    staged in LDS while waiting, flushed coalesced; or streamed flat when the output
+//            IS the (mapped) input span
+// Single launch, inputs read once (round 1: two passes, 1.43 x the algorithmic traffic).
+Status AssembleStrings(CodeGen& cg, KernelPlan* plan, const std::vector<std::string>& expr_strings,
+                       const WordAccumulators& accs, const std::string& decls_before_loop,
+                       const std::string& epilogue_after_loop) {
+  BindStringPlan(cg, plan);
+  const int nv = static_cast<int>(cg.varlen_outs_.size());
+  const int ng = (nv + 1) / 2;
+  int nstage = 0;                              // LDS staging windows per wave
+  for (auto& vo : cg.varlen_outs_) nstage = std::max(nstage, vo.window + 1);
+  const int nhook = static_cast<int>(cg.contains_hooks_.size());
+  plan->num_varlen_outputs = nv;
+  for (auto& vo : cg.varlen_outs_) plan->has_flat_output |= vo.flat_slot >= 0;
+
+  Assembler as{cg, plan, {}};
+  as.Header(expr_strings);
+  std::ostringstream& s = as.src;
+  s << "#define GDV_NV " << nv << "\n#define GDV_NG " << ng << "\n#define GDV_NSTAGE " << std::max(nstage, 1)
+    << "\n#define GDV_NHOOK " << std::max(nhook, 1) << "\n"
+    << "#define GDV_HIT_WORDS (GDV_SPAN_MAX / 64 + 4)\n"
+    << "constexpr bool FULL = false;  // string tiles test `live` at run time (one code path)\n"
+    << "#define GDV_OPTFLAT GDV_OPTFLAT_VALUE\n"
+    << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n"
+    << AblDefine()
+    << "#define GDV_OUT(e, v) if (live) "
+    << (plan->opts.nontemporal ? "gdv_stnt" : "gdv_st") << "(out##e, row, (v))\n";
+
+  s << "GDV_DEV void gdv_tile(const gdv_args& A, const gdv_int64 tile, const gdv_int64 ntiles, const int lane,\n"
+    << "                      const int wave, gdv_uint8* lds_out, gdv_uint64* lds_hit, gdv_uint32 (*lds_tot)[GDV_NV > 0 ? GDV_NV : 1],\n"
+    << "                      gdv_uint64* lds_base) {\n"
+    << "  (void)lds_out; (void)lds_hit; (void)lds_tot; (void)lds_base; (void)ntiles;\n"
+    << kTilePreamble
+    << "  const gdv_int64 wbase = (tile * GDV_WAVES + wave) * GDV_U;\n"
+    << "  const gdv_int64 rbase = wbase * 64;\n"
+    << "  constexpr bool optflat = GDV_OPTFLAT != 0;  // flat outputs: offsets = input offsets, bytes copied after the sweep\n"
+    << "  (void)optflat;\n";
+  if (nv == 0) s << "  if (rbase >= n) return;  // nothing but dead rows (no workgroup barrier below)\n";
+  EmitStringPointersAndLoads(s, cg, plan, true);
+  EmitStringSweep(s, cg, plan);
+
+  // ---- row phase
+  s << "  // ---- rows: fused expression bodies (value for every row, validity per word)\n";
+  for (auto& a : accs.names) s << "  gdv_uint64 " << a << " = 0;\n";
+  s << decls_before_loop;
+  if (nv > 0)
+    s << "  bool need_direct = false;\n"
+      << "  // pass 0: lengths, offsets, staged / flat bytes.  pass 1 (rare): rows of outputs whose bytes\n"
+      << "  // neither fit the LDS window nor are a flat span are recomputed and copied straight to HBM.\n"
+      << "  for (int pass = 0; pass < 2; pass++) {\n"
+      << "  if (pass == 1 && !need_direct) break;\n";
+  else
+    s << "  constexpr int pass = 0;\n  (void)pass;\n";
+  EmitStringRowLoop(s, cg, plan);
+  for (auto& vo : cg.varlen_outs_) s << "    gdv_rot(lc" << vo.e << ");\n";
+  s << "  }\n";
+  if (nv > 0) s << "  if (pass == 1) break;\n";
+  for (auto& vo : cg.varlen_outs_)
+    if (vo.flat_slot >= 0)
+      s << "  if (optflat && fb" << vo.e << " != 0 && lane == 0) gdv_raise_bits(A.err, GDV_ERR_NOTFLAT);\n";
+  s << epilogue_after_loop;
+
+  // ---- var-len outputs
+  if (nv > 0) {
+    // every var-len output is a flat candidate: the optimistic variant needs no totals, no scanner
+    // and no barrier at all — offsets and bytes are already out
+    bool all_flat = true;
+    for (auto& vo : cg.varlen_outs_) all_flat = all_flat && vo.flat_slot >= 0;
+    if (all_flat) s << "  if (!optflat) {  // (all outputs flat: this whole block exists in the general variant only)\n";
+    s << "  // ---- var-len outputs: workgroup totals -> one granule to the scanner\n"
+      << "  if (lane == 0) {\n";
+    for (int v = 0; v < nv; v++)
+      s << "    lds_tot[wave][" << v << "] = (gdv_uint32)run" << cg.varlen_outs_[v].e << ";\n";
+    s << "  }\n  __syncthreads();\n"
+      << "  gdv_uint64 before[GDV_NV], all[GDV_NV];\n"
+      << "#pragma unroll\n  for (int v = 0; v < GDV_NV; v++) { before[v] = 0; all[v] = 0; }\n"
+      << "#pragma unroll\n  for (int w = 0; w < GDV_WAVES; w++) {\n"
+      << "#pragma unroll\n    for (int v = 0; v < GDV_NV; v++) {\n"
+      << "      const gdv_uint32 t = lds_tot[w][v];\n      all[v] += t;\n      before[v] += w < wave ? t : 0u;\n    }\n  }\n"
+      << "  gdv_uint64* const lb_agg = A.mask;\n  gdv_uint64* const lb_pre = A.mask + (gdv_int64)GDV_NG * ntiles;\n"
+      << "  if (threadIdx.x == 0) {\n";
+    for (int g = 0; g < ng; g++)
+      s << "    gdv_lb_post(lb_agg, ntiles, tile, " << g << ", all[" << 2 * g << "], "
+        << (2 * g + 1 < nv ? "all[" + std::to_string(2 * g + 1) + "]" : std::string("0ull")) << ");\n";
+    s << "  }\n";
+    s << "  if (threadIdx.x == 0) {\n"
+      << "#pragma unroll\n    for (int g = 0; g < GDV_NG; g++) lds_base[g] = " << AblSel(32, "(gdv_uint64)tile * 4000", "gdv_lb_wait(lb_pre, ntiles, tile, g, A.err)") << ";\n"
+      << "  }\n  __syncthreads();\n";
+    for (int v = 0; v < nv; v++) {
+      const VarlenOut& vo = cg.varlen_outs_[v];
+      const std::string E = std::to_string(vo.e);
+      s << (vo.flat_slot >= 0 ? "  if (!optflat) {\n" : "  {\n")
+        << "    const gdv_int64 base = (gdv_int64)((lds_base[" << v / 2 << "] >> " << 31 * (v % 2)
+        << ") & GDV_LB_M31) + (gdv_int64)before[" << v << "];\n"
+        << "    const bool fits = run" << E << " < 0x7fffffff && base + run" << E << " <= A.out[" << E << "].cap;\n"
+        << "#pragma unroll\n    for (int u = 0; u < GDV_U; u++) {\n"
+        << "      const gdv_int64 row = rbase + u * 64 + lane;\n"
+        << "      if (row < n) outo" << E << "[row] = (gdv_int32)(base + lc" << E << "[u]);\n"
+        << "    }\n"
+        << "    if (fits) {\n";
+      if (vo.flat_slot >= 0) {
+        const std::string K = std::to_string(vo.flat_slot);
+        s << "      if (fb" << E << " == 0) {  // no row dropped: the output IS the mapped input span\n"
+          << "        gdv_flat_copy(outd" << E << " + base, sd" << K << " + __builtin_amdgcn_readfirstlane(oa" << K
+          << "[0]), run" << E << ", " << vo.flat_map << ", lane);\n"
+          << "      } else {\n";
+      } else if (vo.window >= 0) {
+        s << "      if (run" << E << " <= GDV_OUT_WIN) {\n"
+          << "        " << AblIf(16) << "gdv_flush_out(outd" << E << " + base, win" << E << ", run" << E << ", lane);\n"
+          << "      } else {\n";
+      } else {
+        s << "      {\n";
+      }
+      s << "        dir" << E << " = true;\n        dbase" << E << " = base;\n        need_direct = true;\n"
+        << "      }\n    }\n  }\n";
+    }
+    s << "  if ((gdv_int64)gridDim.x - 1 < ntiles) __syncthreads();  // serial-safe launches only: the LDS hand-off words are reused by the next tile\n";
+    if (all_flat) s << "  }\n";
+    s
+      << "  }  // pass\n";
+  }
+  s << "}\n\n";
+
+  // ---- kernel
+  s << kStringKernelOpen
+    << "  __shared__ __attribute__((aligned(16))) gdv_uint8 gdv_lds_out[GDV_WAVES][GDV_NSTAGE * (GDV_OUT_WIN + 16)];\n"
+    << "  __shared__ __attribute__((aligned(16))) gdv_uint64 gdv_lds_hit[GDV_WAVES][GDV_NHOOK * GDV_HIT_WORDS];\n"
+    << "  __shared__ gdv_uint32 gdv_lds_tot[GDV_WAVES][GDV_NV > 0 ? GDV_NV : 1];\n"
+    << "  __shared__ gdv_uint64 gdv_lds_base[GDV_NG > 0 ? GDV_NG : 1];\n"
+    << "  const gdv_int64 ntiles = (GDV_ROWS(A) + 64 * GDV_U * GDV_WAVES - 1) / (64 * GDV_U * GDV_WAVES);\n";
+  if (nv > 0) {
+    s << "  // workgroup 0 is the scanner of the tile totals; workers are workgroups 1..\n"
+      << "  if (blockIdx.x == 0) {\n"
+      << "    if (wave == 0) {\n"
+      << "      gdv_uint64* const totals = (gdv_uint64*)A.counts;\n"
+      << "      " << (plan->has_flat_output && [&] { for (auto& vo : cg.varlen_outs_) if (vo.flat_slot < 0) return false; return true; }() ? "if (!GDV_OPTFLAT) " : "")
+      << "gdv_scanner<GDV_NG>(A.mask, A.mask + (gdv_int64)GDV_NG * ntiles, ntiles, totals, A.err, lane);\n"
+      << "      if (lane == 0) {\n";
+    for (int v = 0; v < nv; v++) {
+      const VarlenOut& vo = cg.varlen_outs_[v];
+      if (vo.flat_slot >= 0)
+        s << "        if (GDV_OPTFLAT) { const gdv_int32* so = A.in[" << vo.flat_slot << "].offsets; totals[" << v
+          << "] = (gdv_uint64)(so[GDV_ROWS(A)] - so[0]); }\n";
+      s << "        A.out[" << vo.e << "].offsets[GDV_ROWS(A)] = (gdv_int32)(totals[" << v
+        << "] > GDV_LB_M31 ? GDV_LB_M31 : totals[" << v << "]);\n";
+    }
+    s << "      }\n    }\n    return;\n  }\n"
+      << "  for (gdv_int64 tile = (gdv_int64)blockIdx.x - 1; tile < ntiles; tile += (gdv_int64)gridDim.x - 1)\n";
+  } else {
+    s << "  for (gdv_int64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x)\n";
+  }
+  s << "    gdv_tile(A, tile, ntiles, lane, wave, gdv_lds_out[wave], gdv_lds_hit[wave], gdv_lds_tot, gdv_lds_base);\n"
+    << "}\n";
+
+  // Two variants of the same text: GDV_OPTFLAT = 1 (flat outputs taken optimistically; the one
+  // that runs) and, for plans that have flat outputs, GDV_OPTFLAT = 0 (every output through the
+  // scan; compiled only if a batch ever raises NOTFLAT).
+  auto finish = [&](const std::string& tmpl, const char* optflat, std::string* name_out, std::string* src_out) {
+    std::string text = tmpl;
+    size_t p0 = text.find("GDV_OPTFLAT_VALUE");
+    text.replace(p0, strlen("GDV_OPTFLAT_VALUE"), optflat);
+    FinishKernel(std::move(text), /*all_occurrences=*/false, name_out, src_out);
+  };
+  const std::string tmpl = s.str();
+  finish(tmpl, plan->has_flat_output ? "1" : "0", &plan->kernel_name, &plan->source);
+  if (plan->has_flat_output) finish(tmpl, "0", &plan->kernel_name_general, &plan->source_general);
+  plan->ir = plan->source;
+  return Status::OK();
+}
+
+// ------------------------------------------------------------------ string plans, wave shape (round 3)
+// Var-len plans whose output lengths are a function of the input OFFSETS (and of fixed-width
+// inputs) once the bytes are assumed ASCII — substr / left / right / upper / lower / concat /
+// castVARCHAR over columns and literals: C5 — need no hand-off inside the kernel at all:
+//   pre-pass  (kPrepass) the same row bodies reduced to their lengths, views built from the offsets
+//             only: one byte total per wave tile and output -> `counts`
+//   scan      ScanReduce / Spine / Apply over the wave-tile totals (gdv_kernels.hip) -> `mask`
+//   main      (kMain) every WAVE is an independent tile: its output base is one scalar load; no
+//             scanner workgroup, no look-back, no workgroup barrier, no LDS shared between waves;
+//             flat outputs leave straight from the byte sweep's registers
+// Measured on the hand-written prototype (tools/proto/k4h_proto.hip, profiles/r03_k4_experiments.txt):
+// 1.82 ms (scanner shape) -> 0.90-0.97 ms on C5.  The ASCII assumption is checked by the sweep: a
+// tile that breaks it raises NOTASCII and the host re-runs the batch on the scanner-shaped kernel.
+
+Status AssembleStringsWave(CodeGen& cg, KernelPlan* plan, const std::vector<std::string>& expr_strings,
+                           const WordAccumulators& accs, const std::string& decls_before_loop,
+                           const std::string& decls_in_pass, const std::string& after_row_loop,
+                           const std::string& epilogue_after_loop, WaveKind kind, bool has_direct_pass) {
+  BindStringPlan(cg, plan);
+  plan->wave_tiles = true;
+  const bool prepass = kind == WaveKind::kPrepass;
+  cg.sel_ascii_check_ = cg.selection() && !prepass;
+  const int nv = static_cast<int>(cg.varlen_outs_.size());
+  int nstage = 0;
+  for (auto& vo : cg.varlen_outs_) nstage = std::max(nstage, vo.window + 1);
+  // (a pre-pass has hooks only for a swept replace(); the exact variant adds one continuation-byte bitmap
+  // per input whose ASCII flag is consulted)
+  const int ncb = cg.exact_ascii_ ? static_cast<int>(cg.ascii_slots_.size()) : 0;
+  const int nhook = static_cast<int>(cg.contains_hooks_.size()) + ncb;
+  plan->num_varlen_outputs = prepass ? 0 : nv;
+  for (auto& vo : cg.varlen_outs_) plan->has_flat_output |= vo.flat_slot >= 0;
+  const int nin = plan->layout.n_in;
+  const int mirror_slot = cg.mirror_slot_;  // (decided with the tile shape, PlanProjectorShape)
+  if (prepass && mirror_slot < 0 && !cg.exact_ascii_ && !plan->opts.prepass_rolled && !cg.selection())
+    // optimistic pre-pass without a sweep: the body is a few integer operations per row (every general
+    // UTF-8 path folds away under the compile-time ASCII flag) — unrolled, the eight sub-tiles' offsets
+    // are consumed from their registers without the rotation of the rolled loop
+    cg.unroll_rows_ = true;
+
+  Assembler as{cg, plan, {}};
+  // round 6: the main kernel's per-sub-tile sweep (the one with the LDS mirror) takes GDV_SG sub-tiles' spans at a time
+  if (!prepass && mirror_slot >= 0 && !cg.selection() && plan->opts.sweep_group > 1 &&
+      plan->opts.subtiles % plan->opts.sweep_group == 0 && plan->opts.subtiles > plan->opts.sweep_group)
+    as.sweep_group_ = plan->opts.sweep_group;
+  as.Header(expr_strings);
+  std::ostringstream& s = as.src;
+  s << "// " << (prepass ? (cg.exact_ascii_ ? "pre-pass: byte totals per wave tile (exact variant: ASCII flags from a sweep of the bytes)"
+                                            : "pre-pass: byte totals per wave tile from the offsets alone (optimistic ASCII)")
+                         : (cg.exact_ascii_ ? "wave shape, exact variant: ASCII flags per (sub-)tile from the byte sweep"
+                                            : "wave shape: independent wave tiles, output bases from the pre-pass + scan"))
+    << (cg.selection() ? " (rows = the slots of a selection vector: gathered, no byte sweep)" : "")
+    << "\n#define GDV_NV " << nv << "\n#define GDV_NSTAGE " << std::max(nstage, 1)
+    << "\n#define GDV_NHOOK " << (prepass && mirror_slot < 0 && ncb > 0 && plan->opts.prepass_ahead ? "(" + std::to_string(nhook) + " * GDV_U)" : std::to_string(std::max(nhook, 1))) << "\n"
+    << (mirror_slot >= 0 || (prepass && ncb > 0) ? "#define GDV_HIT_WORDS (GDV_SUB_SPAN / 64 + 4)  // match bits of ONE sub-tile's span\n"
+                                                 : "#define GDV_HIT_WORDS (GDV_SPAN_MAX / 64 + 4)\n")
+    << "constexpr bool FULL = false;  // string tiles test `live` at run time (one code path)\n"
+    << AblDefine()
+    << "#define GDV_OUT(e, v) if (live) " << (plan->opts.nontemporal ? "gdv_stnt" : "gdv_st") << "(out##e, row, (v))\n";
+  if (prepass) {
+    // (no staged copies in a pre-pass)
+  } else if (mirror_slot >= 0) {
+    // staged copies read the row's bytes from the LDS mirror of the sub-tile's span when the view
+    // lies inside it (any view of that column does; literals, other columns: HBM as before); a
+    // replace() value answered by the sweep is copied from there along its marked positions
+    const std::string M = std::to_string(mirror_slot);
+    const std::string where = "mir" + M + ", sd" + M + " + sb" + M + ", hm_ok" + M + " ? se" + M + " - sb" + M + " : 0";
+    if (cg.replace_hook_ >= 0)
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mirh") << "(dst, v, " << where << ", hit" << cg.replace_hook_ << ")\n";
+    else
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mir") << "(dst, v, " << where << ")\n";
+  } else {
+    s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n";
+  }
+
+  s << "GDV_DEV void gdv_tile(const gdv_args& A, const gdv_int64 wt, const int lane, const int wave,\n"
+    << "                      gdv_uint8* lds_out, gdv_uint64* lds_hit, gdv_uint8* lds_in) {\n"
+    << "  (void)lds_out; (void)lds_hit; (void)lds_in; (void)wave;\n"
+    << kTilePreamble
+    << "  const gdv_int64 wbase = wt * GDV_U;\n"
+    << "  const gdv_int64 rbase = wbase * 64;\n"
+    << (cg.selection() && !prepass ? [&] {
+         // an EMPTY selection whose count sits in device memory still launches: offsets[0] = 0 is then nobody's row
+         std::string z;
+         for (size_t e = 0; e < plan->output_types.size(); e++)
+           if (plan->output_types[e].is_varlen())
+             z += "  if (n <= 0 && wt == 0 && lane == 0) A.out[" + std::to_string(e) + "].offsets[0] = 0;\n";
+         return z;
+       }() : std::string())
+    << "  if (rbase >= n) return;  // (no barrier anywhere below: waves are independent)\n"
+    << "  const bool last_tile = rbase + 64 * GDV_U >= n;  // the wave tile that holds the batch's last row\n"
+    << "  const gdv_int64 seg_stride = A.aux1;  // wave-tile totals / bases: one array of seg_stride entries per scanned output\n"
+    << "  (void)last_tile; (void)seg_stride;\n";
+  EmitStringPointersAndLoads(s, cg, plan, !prepass, /*wave_shape=*/true);
+  WaveSweepText sweep;
+  if (prepass && mirror_slot < 0) {
+    // views carry the flags the main kernel will give them — the optimistic ASCII flag where a
+    // function consults it — so both kernels compute the same lengths.  Outputs whose length is a
+    // function of the offsets (substr, left, concat ...) read no byte here; others (replace, rtrim,
+    // an if over like ...) read the rows' bytes a first time.
+    for (int k = 0; k < nin; k++) {
+      const DataType& t = cg.schema_[plan->input_fields[k]].type;
+      if (!(t.is_varlen() && cg.needs_values_[k])) continue;
+      if (cg.selection()) {
+        // gathered rows.  Functions that consult the ASCII flag get it OPTIMISTICALLY — their lengths then follow from
+        // the offsets and this pre-pass reads no byte; the main kernel checks every row it copies
+        s << "  const gdv_int32 sfl" << k << " = " << (cg.ascii_slots_.count(k) ? "GDV_STR_ASCII" : "0") << ";\n";
+        continue;
+      }
+      s << "  const gdv_int32 sp1" << k << " = so" << k << "[last_tile ? n : rbase + 64 * GDV_U];\n";
+      if (cg.exact_ascii_ && cg.ascii_slots_.count(k)) {
+        // exact variant: the lengths depend on the bytes now — the pre-pass sweeps every sub-tile's span
+        // (at the top of the row loop) for the pieces that hold a byte >= 0x80; rows take a per-row flag
+        const std::string K = std::to_string(k);
+        cg.row_ascii_slots_.insert(k);
+        s << "  const gdv_int32 inb" << K << " = sd" << K << " + sp1" << K << " + 8 <= slim" << K << " ? GDV_STR_INBUF : 0;\n"
+          << "  const gdv_int32 sfl" << K << " = inb" << K << ";\n";
+        if (plan->opts.prepass_ahead) {
+          // round 5: every sub-tile's span is swept HERE, before the row loop — the first 1024-byte piece of all GDV_U spans
+          // is requested back to back (GDV_U loads in flight per lane where the pipelined form below has one; the sweep is
+          // a dozen instructions, unrolling IT is cheap — unrolling the row body was not), each span's continuation
+          // bytes go to a bitmap of its own, bit u of hiw = sub-tile u's span holds a byte >= 0x80
+          const std::string CB = std::to_string(cg.CbIndex(k));
+          s << "  gdv_uint32 hiw" << K << " = 0;\n"
+            << "  {\n"
+            << "    gdv_int32 sx[GDV_U + 1];  // the sub-tiles' first bytes (wave-uniform); sx[GDV_U] = the tile's end\n"
+            << "#pragma unroll\n"
+            << "    for (int u = 0; u < GDV_U; u++) sx[u] = __builtin_amdgcn_readfirstlane(oa" << K << "[u]);\n"
+            << "    sx[GDV_U] = sp1" << K << ";\n"
+            << "    gdv_uint64 pw[GDV_U][2];\n"
+            << "#pragma unroll\n"
+            << "    for (int u = 0; u < GDV_U; u++) {\n"
+            << "      const gdv_int32 a = sx[u] - (gdv_int32)((gdv_uint64)(sd" << K << " + sx[u]) & 15) + 16 * lane;\n"
+            << "      pw[u][0] = 0ull; pw[u][1] = 0ull;\n"
+            << "      if (a < sx[u + 1]) __builtin_memcpy(pw[u], __builtin_assume_aligned(sd" << K << " + a, 16), 16);\n"
+            << "    }\n"
+            << "#pragma unroll\n"
+            << "    for (int u = 0; u < GDV_U; u++) {\n"
+            << "      const gdv_int32 sb = sx[u] - (gdv_int32)((gdv_uint64)(sd" << K << " + sx[u]) & 15), se = sx[u + 1];\n"
+            << "      const bool fits = se - sb <= GDV_SUB_SPAN;\n"
+            << "      gdv_uint64* const cb = lds_hit + (" << CB << " * GDV_U + u) * GDV_HIT_WORDS;\n"
+            << "      gdv_uint64 sacc = 0, w0 = pw[u][0], w1 = pw[u][1];\n"
+            << "      for (gdv_int32 c = sb; c < se; c += 1024) {\n"
+            << "        const gdv_int32 a = c + 16 * lane;\n"
+            << "        if (c != sb) {  // a span longer than one step (rows of more than 16 bytes on average): loaded as it comes\n"
+            << "          gdv_uint64 t[2] = {0ull, 0ull};\n"
+            << "          if (a < se) __builtin_memcpy(t, __builtin_assume_aligned(sd" << K << " + a, 16), 16);\n"
+            << "          w0 = t[0]; w1 = t[1];\n"
+            << "        }\n"
+            << "        sacc |= w0 | w1;\n"
+            << "        const gdv_uint64 hbw = __ballot(((w0 | w1) & GDV_B80) != 0);\n"
+            << "        const gdv_uint32 cm = hbw != 0 ? gdv_cont_mask16(w0, w1) : 0u;\n"
+            << "        if (fits && a < se) ((gdv_uint16*)cb)[(a - sb) >> 4] = (gdv_uint16)cm;\n"
+            << "      }\n"
+            << "      if (__ballot((sacc & GDV_B80) != 0) != 0) hiw" << K << " |= 1u << u;\n"
+            << "    }\n"
+            << "  }\n"
+            << "  __builtin_amdgcn_wave_barrier();\n";
+          std::ostringstream b;
+          b << "    // exact pre-pass: this sub-tile's continuation-byte bitmap (filled before the loop)\n"
+            << "    const gdv_int32 ss" << K << " = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+            << "    const gdv_int32 se" << K << " = u + 1 < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > 1 ? 1 : 0]) : sp1" << K << ";\n"
+            << "    const gdv_int32 sb" << K << " = ss" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + ss" << K << ") & 15);\n"
+            << "    const bool hm_ok" << K << " = se" << K << " - sb" << K << " <= GDV_SUB_SPAN;  // wave-uniform: the span fits the LDS bitmap\n"
+            << "    const gdv_uint64* const cb" << K << " = lds_hit + (" << CB << " * GDV_U + u) * GDV_HIT_WORDS;\n"
+            << "    const bool hi8_" << K << " = ((hiw" << K << " >> u) & 1u) != 0;\n";
+          sweep.per_sub += b.str();
+          continue;
+        }
+        // software-pipelined like the main kernel's sweep: the first 1024-byte step of the NEXT sub-tile's
+        // span is requested before this sub-tile's rows are looked at (unrolling the loop to have all
+        // eight in flight measured slower: 0.81 vs 0.52 ms at 10^8 rows — the general UTF-8 paths are
+        // inlined into every copy of the body)
+        s << "  gdv_uint64 wn" << K << "[2] = {0ull, 0ull};\n"
+          << "  {\n"
+          << "    const gdv_int32 ss = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+          << "    const gdv_int32 se = GDV_U > 1 ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > 1 ? 1 : 0]) : sp1" << K << ";\n"
+          << "    const gdv_int32 a = ss - (gdv_int32)((gdv_uint64)(sd" << K << " + ss) & 15) + 16 * lane;\n"
+          << "    if (a < se) __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + a, 16), 16);\n"
+          << "  }\n";
+        std::ostringstream b;
+        b << "    // exact pre-pass: the continuation bytes of this sub-tile's span of input " << k << " -> LDS bitmap\n"
+          << "    const gdv_int32 ss" << K << " = __builtin_amdgcn_readfirstlane(oa" << K << "[0]);\n"
+          << "    const gdv_int32 se" << K << " = u + 1 < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > 1 ? 1 : 0]) : sp1" << K << ";\n"
+          << "    const gdv_int32 sb" << K << " = ss" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + ss" << K << ") & 15);\n"
+          << "    const bool hm_ok" << K << " = se" << K << " - sb" << K << " <= GDV_SUB_SPAN;  // wave-uniform: the span fits the LDS bitmap\n"
+          << "    gdv_uint64* const cb" << K << " = lds_hit + " << cg.CbIndex(k) << " * GDV_HIT_WORDS;\n"
+          << "    gdv_uint64 sacc" << K << " = 0;\n"
+          << "    for (gdv_int32 c = sb" << K << "; c < se" << K << "; c += 1024) {\n"
+          << "      const gdv_int32 a = c + 16 * lane;\n"
+          << "      const gdv_uint64 w[2] = {wn" << K << "[0], wn" << K << "[1]};\n"
+          << "      wn" << K << "[0] = 0ull; wn" << K << "[1] = 0ull;\n"
+          << "      if (a + 1024 < se" << K << ") __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + a + 1024, 16), 16);\n"
+          << "      sacc" << K << " |= w[0] | w[1];\n"
+          << "      const gdv_uint64 hbw = __ballot(((w[0] | w[1]) & GDV_B80) != 0);\n"
+          << "      const gdv_uint32 cm = hbw != 0 ? gdv_cont_mask16(w[0], w[1]) : 0u;\n"
+          << "      if (hm_ok" << K << " && a < se" << K << ") ((gdv_uint16*)cb" << K << ")[(a - sb" << K << ") >> 4] = (gdv_uint16)cm;\n"
+          << "    }\n"
+          << "    if (u + 1 < GDV_U) {  // the first piece of the next sub-tile's span\n"
+          << "      const gdv_int32 e2 = u + 2 < GDV_U ? __builtin_amdgcn_readfirstlane(oa" << K << "[GDV_U > 2 ? 2 : 0]) : sp1" << K << ";\n"
+          << "      const gdv_int32 nb = se" << K << " - (gdv_int32)((gdv_uint64)(sd" << K << " + se" << K << ") & 15);\n"
+          << "      if (nb + 16 * lane < e2) __builtin_memcpy(wn" << K << ", __builtin_assume_aligned(sd" << K << " + nb + 16 * lane, 16), 16);\n"
+          << "    }\n"
+          << "    const bool hi8_" << K << " = __ballot((sacc" << K << " & GDV_B80) != 0) != 0;\n"
+          << "    __builtin_amdgcn_wave_barrier();\n";
+        sweep.per_sub += b.str();
+      } else
+        s << "  const gdv_int32 sfl" << k << " = (sd" << k << " + sp1" << k << " + 8 <= slim" << k << " ? GDV_STR_INBUF : 0)"
+          << (cg.ascii_slots_.count(k) ? " | GDV_STR_ASCII" : "") << ";\n";
+    }
+  } else if (mirror_slot >= 0) {
+    EmitWaveSweep(cg, plan, mirror_slot, prepass, &sweep, as.sweep_group_);
+    s << sweep.prologue;
+  } else {
+    EmitWaveTileSweep(s, cg, plan, &sweep.epilogue);
+  }
+
+  s << "  // ---- rows: fused expression bodies (value for every row, validity per word)\n";
+  for (auto& a : accs.names) s << "  gdv_uint64 " << a << " = 0;\n";
+  s << decls_before_loop;
+  if (has_direct_pass)
+    s << "  bool need_direct = false;\n"
+      << "  // pass 0: offsets + bytes staged in LDS.  pass 1 (rare): outputs whose bytes do not fit the\n"
+      << "  // LDS window are recomputed and copied straight to HBM.\n"
+      << "  for (int pass = 0; pass < 2; pass++) {\n"
+      << "  if (pass == 1 && !need_direct) break;\n";
+  else
+    s << "  constexpr int pass = 0;\n  (void)pass;\n";
+  s << decls_in_pass;
+  if (!prepass)
+    // every load issued so far (offsets, validity words, the tile's base, the first piece) is waited
+    // for HERE, once: left to the compiler, the wait lands at the value's first use inside the loop
+    // as a vmcnt(0) that every later iteration pays again — stalling on the previous sub-tile's
+    // stores and on the piece it has just prefetched
+    s << "  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)\n";
+  EmitStringRowLoop(s, cg, plan, /*wave_shape=*/true, sweep.per_sub);
+  s << "  }\n";
+  if (has_direct_pass) s << "  if (pass == 1) break;\n";
+  s << sweep.epilogue;
+  s << after_row_loop;
+  if (!prepass && !has_direct_pass)
+    // the epilogue's pointers (validity words, closing offsets, totals) are read from the argument
+    // block HERE, not hoisted above the row loop where they would sit in — or be spilled from —
+    // scalar registers for the whole tile: the block's address goes through an opaque zero
+    s << "  {\n  gdv_int64 gdv_z = 0;\n  asm volatile(\"\" : \"+s\"(gdv_z));\n"
+      << "  const gdv_args& A_late = *(const gdv_args*)((const gdv_uint8*)&A + gdv_z);\n"
+      << "  {\n  const gdv_args& A = A_late;\n"
+      << epilogue_after_loop << "  }\n  }\n";
+  else
+    s << epilogue_after_loop;
+  if (has_direct_pass) s << "  }  // pass\n";
+  s << "}\n\n";
+
+  s << kStringKernelOpen;
+  if (prepass)
+    // (a pre-pass tile is a few loads and one store: waves walk several tiles, grid-stride)
+    s << (mirror_slot >= 0 || ncb > 0 ? "  __shared__ __attribute__((aligned(16))) gdv_uint64 gdv_lds_hit[GDV_WAVES][GDV_NHOOK * GDV_HIT_WORDS];\n" : "")
+      << "  const gdv_int64 nwt = (GDV_ROWS(A) + 64 * GDV_U - 1) / (64 * GDV_U);\n"
+      << "  for (gdv_int64 wt = (gdv_int64)blockIdx.x * GDV_WAVES + wave; wt < nwt; wt += (gdv_int64)gridDim.x * GDV_WAVES)\n"
+      << "    gdv_tile(A, wt, lane, wave, nullptr, " << (mirror_slot >= 0 || ncb > 0 ? "gdv_lds_hit[wave]" : "nullptr") << ", nullptr);\n";
+  else
+    s << "  __shared__ __attribute__((aligned(16))) gdv_uint8 gdv_lds_out[GDV_WAVES][GDV_NSTAGE * (GDV_OUT_WIN + 16)];\n"
+      << "  __shared__ __attribute__((aligned(16))) gdv_uint64 gdv_lds_hit[GDV_WAVES][GDV_NHOOK * GDV_HIT_WORDS];\n"
+      << (mirror_slot >= 0 ? "  __shared__ __attribute__((aligned(16))) gdv_uint8 gdv_lds_in[GDV_WAVES][GDV_SUB_SPAN + 32];\n" : "")
+      << "  gdv_tile(A, (gdv_int64)blockIdx.x * GDV_WAVES + wave, lane, wave, gdv_lds_out[wave], gdv_lds_hit[wave], "
+      << (mirror_slot >= 0 ? "gdv_lds_in[wave]" : "nullptr") << ");\n";
+  s << "}\n";
+
+  FinishKernel(s.str(), /*all_occurrences=*/false, &plan->kernel_name, &plan->source);
+  plan->ir = plan->source;
+  return Status::OK();
+}
+
+}  // namespace gdv::planner

@@ -323,7 +323,7 @@ FunctionRegistry::FunctionRegistry() {
   add("substring", {utf8(), int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult,
       "substr_utf8_int64");
   // concat (null argument = empty string, never null) and || (null if any argument is null),
-  // 2..6 arguments; planned as a list of pieces, not as a call (gdv_planner.cc)
+  // 2..6 arguments; planned as a list of pieces, not as a call (gdv_codegen_functions.cc, GenConcat)
   for (int nargs = 2; nargs <= 6; nargs++) {
     std::vector<DataType> ps(nargs, utf8());
     add("concat", ps, utf8(), NullPolicy::kNullNever, kVarlenResult, "gdv_concat");
@@ -346,8 +346,8 @@ FunctionRegistry::FunctionRegistry() {
     for (const char* f : {"hashMD5", "md5"}) add(f, {t}, utf8(), NullPolicy::kNullNever, kVarlenResult, Sym("hashMD5", {t}));
   }
   add("replace", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext,
-      "gdv_replace");  // planned by gdv_planner.cc (literal from / to: a table + the sweep's match bits; otherwise per row)
-  // lpad / rpad: planned as two pieces (gdv_planner.cc); a length / fill that is not a literal: the fill read cyclically, per row
+      "gdv_replace");  // planned by gdv_codegen_functions.cc, GenReplace (literal from / to: a table + the sweep's match bits; otherwise per row)
+  // lpad / rpad: planned as two pieces (gdv_codegen_functions.cc, GenPad); a length / fill that is not a literal: the fill read cyclically, per row
   for (const char* f : {"lpad", "rpad"}) {
     add(f, {utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_pad");
     add(f, {utf8(), int32(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_pad");
@@ -360,7 +360,7 @@ FunctionRegistry::FunctionRegistry() {
   add("space", {int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
   add("space", {int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
   add("translate", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext,
-      "gdv_translate");  // planned by gdv_planner.cc
+      "gdv_translate");  // planned by gdv_codegen_functions.cc, GenTranslate
   // bytes <-> printable text and checksums: hex / to_hex, unhex / from_hex, base64, unbase64 are values the output copy
   // materialises (GDV_MAP_ENCODE; the decoders raise on text they do not take), crc32 is the zlib CRC-32 widened to int64.
   // [RFC 4648 / zlib pin the bytes; letter case, raising and the widening are recalled: PARITY.md, hex / base64 / crc32]

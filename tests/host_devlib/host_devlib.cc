@@ -183,7 +183,7 @@ long host_str_view(int fn, const int* off, const unsigned char* data, long size,
   }
   return at;
 }
-// general LIKE matcher over a pattern compiled the way gdv_planner.cc compiles it
+// general LIKE matcher over a pattern compiled the way gdv_codegen_functions.cc (CompileLike) compiles it
 void host_str_like(const int* off, const unsigned char* data, long size, long n, const unsigned char* pbyte,
                    const unsigned char* pkind, int plen, int map, unsigned char* out) {
   HostCol c{off, data, size};
