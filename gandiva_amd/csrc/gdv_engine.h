@@ -18,6 +18,12 @@
 
 namespace gdv {
 
+namespace engine {  // gdv_engine_internal.h
+class ArgBlock;
+struct Staging;
+class VarlenLaunch;
+}  // namespace engine
+
 enum class MemKind : int32_t {
   kHost = 0,    // buffers are host memory: staged to HBM, results copied back (correctness path)
   kDevice = 1,  // buffers are HBM-resident on the current device: zero-copy (the fast path)
@@ -148,6 +154,15 @@ class Projector {
                             OutputBuffers* outs, int num_outs, hipStream_t stream, void* result, const void* rows_word) const;
   Status EvaluateAsyncTwoStage(int64_t num_rows, const ColumnBuffers* cols, int num_cols, const SelectionView* sel,
                                OutputBuffers* outs, int num_outs, hipStream_t stream, void* result) const;
+  // the parts of Evaluate (gdv_projector.cc)
+  Status BindOutputs(int64_t out_rows, OutputBuffers* outs, int num_outs, MemKind mem, hipStream_t stream,
+                     engine::ArgBlock& args, engine::Staging& st, std::vector<void*>& dev_data, std::vector<void*>& dev_valid,
+                     std::vector<void*>& dev_offs) const;
+  Status LaunchVarlen(engine::VarlenLaunch& vlaunch, engine::ArgBlock& args, std::vector<uint64_t>& back,
+                      std::vector<uint64_t>& seg, uint32_t& err_bits, hipStream_t stream) const;
+  Status EvaluateVarlen(engine::VarlenLaunch& vlaunch, engine::ArgBlock& args, engine::Staging& st, OutputBuffers* outs,
+                        MemKind mem, int64_t out_rows, std::vector<void*>& dev_data, std::vector<uint64_t>& totals,
+                        uint32_t& err_bits, hipStream_t stream) const;
 
  public:
 

@@ -65,7 +65,7 @@ struct CodegenOptions {
 };
 
 // Byte layout of the single by-value kernel argument (struct gdv_args in the generated
-// source).  Host (gdv_engine.cc) and device agree on this through these offsets only.
+// source).  Host (ArgBlock, gdv_engine_internal.h) and device agree on this through these offsets only.
 struct ArgLayout {
   static constexpr int kHeaderBytes = 64;  // n, err, sel, mask, counts, aux0..2
   static constexpr int kOffN = 0, kOffErr = 8, kOffSel = 16, kOffMask = 24, kOffCounts = 32,

@@ -1086,3 +1086,99 @@ def test_an_empty_selection_whose_count_sits_in_device_memory():
     assert len(got) == 0
     got.validate(full=True)
     assert int(outs[0].offsets[:4].view(torch.int32)[0]) == 0
+
+
+# ------------------------------------------------------------------ one var-len launch for the synchronous and the asynchronous entry
+
+def _c5_variant(n, what):
+    """C5's column over n rows: "ascii"; "utf8" = one two-byte character (C3 A9) in the middle row; "dirty" = NULL
+    rows (the first, and a tenth of the others) that KEEP their bytes."""
+    offsets, data, _ = W.c5_numpy(n)
+    validity = None
+    if what == "utf8":
+        at = int(offsets[n // 2])                 # (every row holds at least 4 bytes)
+        data[at], data[at + 1] = 0xC3, 0xA9
+    if what == "dirty":
+        mask = np.random.default_rng(5).random(n) < 0.1
+        mask[0] = True
+        validity = pa.py_buffer(np.packbits(~mask, bitorder="little"))
+    arr = pa.Array.from_buffers(pa.string(), n, [validity, pa.py_buffer(offsets), pa.py_buffer(data)])
+    return pa.RecordBatch.from_arrays([arr], schema=W.c5_schema())
+
+
+def _upper_alone():
+    b = gandiva.TreeExprBuilder()
+    s = b.make_field(W.c5_schema().field(0))
+    return [b.make_expression(b.make_function("upper", [s], pa.string()), pa.field("up", pa.string()))]
+
+
+def _back_to_path_0(proj, ascii_batch):
+    for _ in range(17):   # (projectors are cached per plan: an earlier test, or this one, may have left it on path 1 or 2)
+        if proj.path_hint == 0:
+            break
+        proj.evaluate(ascii_batch)
+    assert proj.path_hint == 0
+
+
+def _assert_sync_and_async_give_the_same_bytes(proj, dbatch, rows, what, selection=None):
+    """evaluate_device and evaluate_device_async over the same device batch, on the path the projector is on after
+    the synchronous call: validity and bool bits of the rows, the rows + 1 offsets, the byte totals and the bytes."""
+    import torch
+    sync = proj.evaluate_device(dbatch, selection=selection)
+    torch.cuda.synchronize()
+    hint = proj.path_hint
+    asyn, result = proj.evaluate_device_async(dbatch, selection=selection)
+    torch.cuda.synchronize()
+    assert proj.path_hint == hint                     # an asynchronous call does not move the projector
+    assert int(result[0]) == 0, f"{what}: asynchronous status {int(result[0])} on path {hint}"
+
+    def bits(t):
+        return np.unpackbits(t.cpu().numpy(), bitorder="little")[:rows]
+    for i, (s, a) in enumerate(zip(sync, asyn)):
+        assert np.array_equal(bits(s.validity), bits(a.validity)), f"{what}: validity of output {i}"
+        if s.offsets is None:
+            assert pa.types.is_boolean(s.type)
+            assert np.array_equal(bits(s.data), bits(a.data)), f"{what}: values of output {i}"
+            assert int(result[1 + i]) == 0
+            continue
+        nb = (rows + 1) * 4
+        assert torch.equal(s.offsets[:nb], a.offsets[:nb]), f"{what}: offsets of output {i}"
+        total = int(result[1 + i])
+        assert total == s.data_used, f"{what}: byte total of output {i}"
+        assert torch.equal(s.data[:total], a.data[:total]), f"{what}: bytes of output {i}"
+    return hint
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", [1, 63, 65, 40_000])
+@pytest.mark.parametrize("plan", ["c5", "upper"])
+def test_synchronous_and_asynchronous_var_len_evaluations_give_the_same_bytes(plan, rows):
+    """Both entries enqueue the same kernels: C5 (wave shape with a pre-pass) and upper(col) alone (flat output,
+    scanner shape), on each of the three paths — an ASCII batch on the optimistic kernels (0), a batch with a byte
+    >= 0x80 once the synchronous call has moved a plan with an exact variant there (1), a batch whose NULL rows hold
+    bytes on the general kernel (2).  Rows: one, either side of a 64-row word, several tiles with a partial last one."""
+    exprs = W.c5_expressions() if plan == "c5" else _upper_alone()
+    proj = gandiva.make_projector(W.c5_schema(), exprs, pa.default_memory_pool())
+    ascii_batch = _c5_variant(rows, "ascii")
+    _back_to_path_0(proj, ascii_batch)
+    try:
+        for what, want in (("ascii", 0), ("utf8", 1 if plan == "c5" else None), ("dirty", 2)):
+            db = gandiva.DeviceBatch.from_arrow(_c5_variant(rows, what))
+            hint = _assert_sync_and_async_give_the_same_bytes(proj, db, rows, f"{plan}, {rows} rows, {what}")
+            if want is not None:
+                assert hint == want, f"{plan}, {rows} rows, {what}: path {hint}"
+    finally:
+        _back_to_path_0(proj, ascii_batch)            # leave the cached projector on the fast path
+
+
+@pytest.mark.gpu
+def test_synchronous_and_asynchronous_var_len_evaluations_give_the_same_bytes_under_a_selection_vector():
+    """The same under a uint32 selection vector of 1000 slots out of 40 000 rows: the pre-pass of the asynchronous
+    call walks the slots the main kernel walks."""
+    import torch
+    rows, slots = 40_000, 1000
+    proj = gandiva.make_projector(W.c5_schema(), W.c5_expressions(), pa.default_memory_pool(), "UINT32")
+    picked = np.sort(np.random.default_rng(9).choice(rows, slots, replace=False)).astype(np.int32)
+    sel = gandiva.SelectionVector(2, torch.from_numpy(picked).cuda(), slots, device=True)
+    db = gandiva.DeviceBatch.from_arrow(_c5_variant(rows, "ascii"))
+    _assert_sync_and_async_give_the_same_bytes(proj, db, slots, "C5 under a uint32 selection", selection=sel)
