@@ -19,10 +19,12 @@ OUT_DIR = os.path.join(PKG, "_pyarrow")
 
 def build(force=False):
     """pyarrow's gandiva.pyx -> _pyarrow/gandiva.<abi>.so (returned), and this directory's host_pool.pyx (a
-    pyarrow.MemoryPool over gandiva::HostMemoryPool) -> _pyarrow/host_pool.<abi>.so."""
+    pyarrow.MemoryPool over gandiva::HostMemoryPool) -> _pyarrow/host_pool.<abi>.so and device_memory.pyx (a
+    pyarrow.MemoryManager over gandiva::HipMemoryManager) -> _pyarrow/device_memory.<abi>.so."""
     pa_dir = os.path.dirname(pa.__file__)
     out = _build_one(os.path.join(pa_dir, "gandiva.pyx"), "gandiva", force)
     _build_one(os.path.join(HERE, "host_pool.pyx"), "host_pool", force)
+    _build_one(os.path.join(HERE, "device_memory.pyx"), "device_memory", force)
     return out
 
 

@@ -1,6 +1,9 @@
 // gandiva/projector.h (pyarrow/includes/libgandiva.pxd:214-240).  Evaluate launches the fused
 // HIP kernel; batches whose buffers are HBM-resident (arrow::Buffer::is_cpu() == false) are
 // used in place and the outputs are allocated from the same arrow::MemoryManager.
+// gandiva/device_memory.h provides that manager (HipMemoryManager: RecordBatch::CopyTo(mm) puts a
+// batch into HBM); its batches are evaluated on the manager's device, and the calling thread's
+// device is restored on return.  With such a batch the MemoryPool argument is not used.
 #pragma once
 #include "gandiva/arrow.h"
 #include "gandiva/configuration.h"

@@ -11,7 +11,9 @@
 
 #include "arrow/api.h"
 #include "arrow/device.h"
+#include "device_scope.h"
 #include "gandiva/condition.h"
+#include "gandiva/device_memory.h"
 #include "gandiva/configuration.h"
 #include "gandiva/expression_registry.h"
 #include "gandiva/filter.h"
@@ -170,12 +172,45 @@ arrow::Result<std::shared_ptr<arrow::Buffer>> AllocOut(int64_t bytes, bool devic
   if (bytes < 8) bytes = 8;
   if (device) {
     if (!mm) return Status::Invalid("device-resident batch without a MemoryManager");
+    // Not cleared (the host path's memset below zeroes what the staging copy does not bring back): the kernels store
+    // the validity of all the output rows in whole 8-byte words and every offset, so everything an Arrow reader looks
+    // at is written; value slots under a null and the bytes behind the last word — a recycled pool block's — are
+    // unspecified, as Arrow allows.
     ARROW_ASSIGN_OR_RAISE(auto b, mm->AllocateBuffer(bytes));
     return std::shared_ptr<arrow::Buffer>(std::move(b));
   }
   ARROW_ASSIGN_OR_RAISE(auto b, arrow::AllocateBuffer(bytes, pool ? pool : arrow::default_memory_pool()));
   std::memset(b->mutable_data(), 0, static_cast<size_t>(b->size()));
   return std::shared_ptr<arrow::Buffer>(std::move(b));
+}
+
+// The library device a batch in `mm`'s memory is evaluated on; -1 (the calling thread's device, as before
+// gandiva/device_memory.h existed) for host batches and for buffers of somebody else's MemoryManager.
+int HipDeviceOf(const std::shared_ptr<arrow::MemoryManager>& mm) {
+  auto hip = dynamic_cast<const HipMemoryManager*>(mm.get());
+  return hip ? hip->device_id() : -1;
+}
+
+// The selection vector of a selection-mode Evaluate as the C ABI takes it.  A CPU vector over a device-resident batch —
+// what pyarrow's Filter.evaluate hands out, it allocates from a MemoryPool — is uploaded into `*staged`; a device
+// vector over a host batch is refused (the kernel would be handed host addresses as device ones).
+Status BindSelection(const SelectionVector& selection, bool batch_device, const std::shared_ptr<arrow::MemoryManager>& mm,
+                     gdv_selection_t* sel, std::shared_ptr<arrow::Buffer>* staged) {
+  const arrow::Buffer& buf = selection.GetBuffer();
+  std::memset(sel, 0, sizeof(*sel));
+  sel->mode = static_cast<int32_t>(selection.GetMode());
+  sel->num_slots = selection.GetNumSlots();
+  sel->indices = reinterpret_cast<const void*>(buf.address());
+  if (buf.is_cpu() && batch_device) {
+    if (!mm) return Status::Invalid("device-resident batch without a MemoryManager");
+    arrow::Buffer used(buf.data(), selection.GetNumSlots() * selection.index_bytes());
+    ARROW_ASSIGN_OR_RAISE(auto up, arrow::MemoryManager::CopyNonOwned(used, mm));
+    *staged = std::move(up);
+    sel->indices = reinterpret_cast<const void*>((*staged)->address());
+  } else if (!buf.is_cpu() && !batch_device) {
+    return Status::Invalid("batch and selection vector must live in the same memory domain");
+  }
+  return Status::OK();
 }
 
 }  // namespace
@@ -575,12 +610,10 @@ Status Projector::Evaluate(const arrow::RecordBatch& batch, const SelectionVecto
   ARROW_RETURN_NOT_OK(MarshalBatch(batch, schema_, &cols, &device, &mm));
   const int64_t out_rows = selection ? selection->GetNumSlots() : batch.num_rows();
   gdv_selection_t sel;
-  if (selection) {
-    sel.mode = static_cast<int32_t>(selection->GetMode());
-    sel.indices = reinterpret_cast<const void*>(selection->GetBuffer().address());
-    sel.num_slots = selection->GetNumSlots();
-    if (!selection->GetBuffer().is_cpu()) device = true;
-  }
+  std::shared_ptr<arrow::Buffer> sel_staged;
+  if (selection) ARROW_RETURN_NOT_OK(BindSelection(*selection, device, mm, &sel, &sel_staged));
+  internal::DeviceScope on_device(HipDeviceOf(mm));  // a HipMemoryManager's batch runs on that manager's device
+  ARROW_RETURN_NOT_OK(on_device.status());
   const int n_out = static_cast<int>(output_fields_.size());
   const int mem = device ? GDV_MEM_DEVICE : GDV_MEM_HOST;
   std::vector<gdv_out_column_t> outs(n_out);
@@ -656,12 +689,10 @@ Status Projector::Evaluate(const arrow::RecordBatch& batch, const SelectionVecto
   ARROW_RETURN_NOT_OK(MarshalBatch(batch, schema_, &cols, &device, &mm));
   const int64_t out_rows = selection ? selection->GetNumSlots() : batch.num_rows();
   gdv_selection_t sel;
-  if (selection) {
-    sel.mode = static_cast<int32_t>(selection->GetMode());
-    sel.indices = reinterpret_cast<const void*>(selection->GetBuffer().address());
-    sel.num_slots = selection->GetNumSlots();
-    if (!selection->GetBuffer().is_cpu()) device = true;
-  }
+  std::shared_ptr<arrow::Buffer> sel_staged;
+  if (selection) ARROW_RETURN_NOT_OK(BindSelection(*selection, device, mm, &sel, &sel_staged));
+  internal::DeviceScope on_device(HipDeviceOf(mm));  // a HipMemoryManager's batch runs on that manager's device
+  ARROW_RETURN_NOT_OK(on_device.status());
   const int mem = device ? GDV_MEM_DEVICE : GDV_MEM_HOST;
   std::vector<gdv_out_column_t> outs(n_out);
   for (int e = 0; e < n_out; e++) {
@@ -761,13 +792,31 @@ Status Filter::Evaluate(const arrow::RecordBatch& batch, std::shared_ptr<Selecti
     return Status::Invalid("Selection vector too small: max slots ", out->GetMaxSlots(),
                            " < number of rows ", batch.num_rows());
   const bool out_device = !out->GetBuffer().is_cpu();
-  if (out_device != device)
+  if (out_device && !device)
     return Status::Invalid("batch and selection vector must live in the same memory domain");
+  internal::DeviceScope on_device(HipDeviceOf(mm));
+  ARROW_RETURN_NOT_OK(on_device.status());
+  // A CPU vector over a device-resident batch (pyarrow's Filter.evaluate allocates its vector from a MemoryPool):
+  // the indices are written next to the batch and the selected ones — a slice, not the whole vector — are copied
+  // into the caller's.
+  std::shared_ptr<arrow::Buffer> staged;
+  void* indices = reinterpret_cast<void*>(out->GetBuffer().address());
+  int64_t max_slots = out->GetMaxSlots();
+  if (device && !out_device) {
+    ARROW_ASSIGN_OR_RAISE(staged, AllocOut(batch.num_rows() * out->index_bytes(), true, nullptr, mm));
+    indices = reinterpret_cast<void*>(staged->address());
+    max_slots = batch.num_rows();
+  }
   int64_t count = 0;
   GDV_CXX_RETURN_NOT_OK(gdv_filter_evaluate(
       handle_, batch.num_rows(), cols.data(), static_cast<int>(cols.size()), static_cast<int>(out->GetMode()),
-      reinterpret_cast<void*>(out->GetBuffer().address()), out->GetMaxSlots(), &count,
-      device ? GDV_MEM_DEVICE : GDV_MEM_HOST, nullptr));
+      indices, max_slots, &count, device ? GDV_MEM_DEVICE : GDV_MEM_HOST, nullptr));
+  if (staged && count > 0) {
+    const int64_t bytes = count * out->index_bytes();
+    ARROW_ASSIGN_OR_RAISE(auto selected, arrow::MemoryManager::CopyBuffer(arrow::SliceBuffer(staged, 0, bytes),
+                                                                          arrow::default_cpu_memory_manager()));
+    std::memcpy(out->GetBuffer().mutable_data(), selected->data(), static_cast<size_t>(bytes));
+  }
   out->SetNumSlots(count);
   return Status::OK();
 }
@@ -861,6 +910,8 @@ Status ShardedProjector::Evaluate(const std::vector<std::shared_ptr<arrow::Recor
     std::shared_ptr<arrow::MemoryManager> mm;
     ARROW_RETURN_NOT_OK(MarshalBatch(*shards[s], p.schema_, &cols[s], &device, &mm));
     if (!device) return Status::Invalid("shard ", s, " is host-resident: pass ONE host batch to the other overload");
+    if (HipDeviceOf(mm) >= 0 && HipDeviceOf(mm) != devices_[s])
+      return Status::Invalid("shard ", s, " lives on device ", HipDeviceOf(mm), ", devices[", s, "] is ", devices_[s]);
     vbuf[s].resize(n_out); dbuf[s].resize(n_out); obuf[s].resize(n_out);
     int64_t varlen_guess = 64;
     for (auto& c : cols[s]) if (c.offsets) varlen_guess += c.data_size;
@@ -949,6 +1000,11 @@ Status ShardedFilter::Evaluate(const std::vector<std::shared_ptr<arrow::RecordBa
     ARROW_RETURN_NOT_OK(MarshalBatch(*shards[s], filter_->schema_, &cols[s], &device, &mm));
     if (!outs[s] || outs[s]->GetMode() != outs[0]->GetMode()) return Status::Invalid("selection vectors of one mode are required");
     if (!device || outs[s]->GetBuffer().is_cpu()) return Status::Invalid("shard ", s, ": batch and selection vector must be device-resident");
+    if (HipDeviceOf(mm) >= 0 && HipDeviceOf(mm) != devices_[s])
+      return Status::Invalid("shard ", s, " lives on device ", HipDeviceOf(mm), ", devices[", s, "] is ", devices_[s]);
+    const int sel_device = HipDeviceOf(outs[s]->GetBuffer().memory_manager());
+    if (sel_device >= 0 && sel_device != devices_[s])
+      return Status::Invalid("selection vector ", s, " lives on device ", sel_device, ", devices[", s, "] is ", devices_[s]);
     std::memset(&sh[s], 0, sizeof(gdv_shard_t));
     sh[s].device = devices_[s];
     sh[s].cols = cols[s].data();
@@ -1042,6 +1098,8 @@ Status FilterProject::Evaluate(const arrow::RecordBatch& batch, arrow::MemoryPoo
   ARROW_RETURN_NOT_OK(MarshalBatch(batch, schema_, &cols, &device, &mm));
   if (out_selection && (!out_selection->GetBuffer().is_cpu()) != device)
     return Status::Invalid("batch and selection vector must live in the same memory domain");
+  internal::DeviceScope on_device(HipDeviceOf(mm));
+  ARROW_RETURN_NOT_OK(on_device.status());
   const int n_out = static_cast<int>(output_fields_.size());
   const int mem = device ? GDV_MEM_DEVICE : GDV_MEM_HOST;
   const int64_t rows = batch.num_rows();

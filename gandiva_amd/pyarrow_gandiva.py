@@ -17,7 +17,15 @@ page-locked block (two memcpys + two DMA copies: 103-133 us per 16K-row batch); 
     proj = gandiva.make_projector(batch.schema, exprs, pool)   # outputs are allocated from `pool`
     out, = proj.evaluate(batch)                          # nothing is staged: pyarrow_gandiva.host_staged_bytes() stays put
 
-HBM-resident batches (`gandiva_amd.DeviceBatch`, the Arrow C Device Data Interface) skip the host link altogether.
+HBM-resident batches skip the host link altogether.  `hip_memory_manager()` is a `pyarrow.MemoryManager` over the HBM
+of one GPU (gandiva::HipMemoryManager), so plain pyarrow carries them:
+
+    mm = pyarrow_gandiva.hip_memory_manager()            # device 0
+    dbatch = batch.copy_to(mm)                           # host -> HBM, once
+    out, = proj.evaluate(dbatch)                         # evaluated in place; out.is_cpu is False, nothing is copied
+    host = out.copy_to(pa.default_cpu_memory_manager())  # only when the host wants to look
+
+(`gandiva_amd.DeviceBatch` and the Arrow C Device Data Interface are the routes that need no pyarrow.gandiva.)
 """
 import importlib.machinery
 import importlib.util
@@ -66,8 +74,29 @@ def host_staged_bytes():
     return _host_pool_module().host_staged_bytes()
 
 
+def hip_memory_manager(device=0):
+    """The `pyarrow.MemoryManager` of library device `device` (gandiva::HipMemoryManager): `batch.copy_to(mm)` puts a
+    batch into that GPU's HBM, `pyarrow.gandiva` projectors / filters evaluate it in place and allocate their outputs
+    from the same manager, `array.copy_to(pa.default_cpu_memory_manager())` brings a result back."""
+    return _extension("device_memory").hip_memory_manager(device)
+
+
+def reserved_bytes(device=0):
+    """(total, in_use) bytes of the device pool behind `hip_memory_manager(device)`."""
+    return _extension("device_memory").reserved_bytes(device)
+
+
+def trim(device=0):
+    """Give the buffers that pool retains (dropped, not yet reused) back to the driver."""
+    return _extension("device_memory").trim(device)
+
+
 def _host_pool_module():
-    name = "gandiva_amd._pyarrow_host_pool"
+    return _extension("host_pool")
+
+
+def _extension(ext):
+    name = "gandiva_amd._pyarrow_" + ext
     if name in sys.modules:
         return sys.modules[name]
     load()
@@ -76,9 +105,9 @@ def _host_pool_module():
         import build_pyarrow_gandiva as b
     finally:
         sys.path.pop(0)
-    path = os.path.join(b.OUT_DIR, "host_pool" + __import__("sysconfig").get_config_var("EXT_SUFFIX"))
-    loader = importlib.machinery.ExtensionFileLoader("host_pool", path)
-    spec = importlib.util.spec_from_file_location("host_pool", path, loader=loader)
+    path = os.path.join(b.OUT_DIR, ext + __import__("sysconfig").get_config_var("EXT_SUFFIX"))
+    loader = importlib.machinery.ExtensionFileLoader(ext, path)
+    spec = importlib.util.spec_from_file_location(ext, path, loader=loader)
     mod = importlib.util.module_from_spec(spec)
     loader.exec_module(mod)
     sys.modules[name] = mod
