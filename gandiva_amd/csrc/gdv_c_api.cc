@@ -1569,6 +1569,24 @@ char* gdv_tier0_program(const gdv_schema_t* schema, gdv_expression_t* const* exp
     return DupString(text);
   });
 }
+char* gdv_tier0_program_selection(const gdv_schema_t* schema, gdv_expression_t* const* exprs, int num_exprs, int selection_mode) {
+  return GuardedPtr([&]() -> char* {
+    if (!schema || !exprs || num_exprs < 1) return FailPtr<char>("schema and expressions are required");
+    if (selection_mode < 0 || selection_mode > 3) return FailPtr<char>("selection mode must be 0 (none), 1 (uint16), 2 (uint32) or 3 (uint64)");
+    std::vector<ExpressionPtr> v;
+    for (int i = 0; i < num_exprs; i++) {
+      if (!exprs[i]) return FailPtr<char>("null expression");
+      v.push_back(exprs[i]->expr);
+    }
+    std::string text;
+    Status st = Tier0Describe(schema->fields, v, /*is_condition=*/false, &text, static_cast<SelectionMode>(selection_mode));
+    if (!st.ok()) {
+      Fail(st);
+      return nullptr;
+    }
+    return DupString(text);
+  });
+}
 int64_t gdv_tier0_launches(void) { return Tier0Launches(); }
 void gdv_shutdown(void) { Runtime::ShutdownBackgroundCompiler(); }
 

@@ -352,24 +352,10 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
         out->v = e.empty() ? std::string("false") : Tmp("bool", e);
         return Status::OK();
       }
-      std::vector<uint64_t> vals;
-      uint64_t mask = vt.byte_width() >= 8 ? ~0ull : ((1ull << (8 * vt.byte_width())) - 1);
+      // value equality, as a hash set of floats gives it: -0.0 and +0.0 are one value, a NaN equals nothing (the probe adds
+      // +0.0, which maps -0.0 to +0.0 and keeps NaNs NaN)
+      const std::vector<uint64_t> vals = InListBitImages(vt, n.values());
       const bool is_fp = vt.id == kFloat || vt.id == kDouble;
-      for (auto& l : n.values()) {
-        uint64_t bits = l.lo & mask;
-        if (is_fp) {
-          // value equality, as a hash set of floats gives it: -0.0 and +0.0 are one value,
-          // a NaN equals nothing (the probe adds +0.0, which maps -0.0 to +0.0 and keeps NaNs NaN)
-          const bool nan = vt.id == kFloat ? ((bits & 0x7f800000u) == 0x7f800000u && (bits & 0x7fffffu) != 0)
-                                           : ((bits & 0x7ff0000000000000ull) == 0x7ff0000000000000ull &&
-                                              (bits & 0xfffffffffffffull) != 0);
-          if (nan) continue;
-          if (bits == (vt.id == kFloat ? 0x80000000ull : 0x8000000000000000ull)) bits = 0;
-        }
-        vals.push_back(bits);
-      }
-      std::sort(vals.begin(), vals.end());
-      vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
       const std::string probe = is_fp ? "gdv_bits64(" + x.v + " + (" + vt.CType() + ")0)" : "gdv_bits64(" + x.v + ")";
       if (vals.empty()) {
         out->v = "false";

@@ -355,16 +355,19 @@ bool Filter::UseTier0() const { return Tier0Active(tier0_.get(), &tier0_pending_
 
 // ------------------------------------------------------------------ tier 0: the program of a plan as text (no device)
 
-Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exprs, bool is_condition, std::string* text) {
+Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exprs, bool is_condition, std::string* text,
+                     SelectionMode mode) {
   KernelPlan plan;
   StagedExpressions staged;
   StageMaterialisedValues(schema, exprs, &staged);
   if (!staged.pre.empty()) return Status::NotImplemented("no tier 0: the plan materialises values in a first stage");
   if (is_condition) {
     if (exprs.size() != 1) return Status::Invalid("one condition expected");
+    if (mode != SelectionMode::kNone) return Status::Invalid("a filter has no selection mode");
     GDV_RETURN_NOT_OK(PlanFilter(schema, exprs[0], CodegenOptions::FromEnv(), &plan));
   } else {
-    GDV_RETURN_NOT_OK(PlanProjector(schema, exprs, SelectionMode::kNone, CodegenOptions::FromEnv(), &plan));
+    GDV_RETURN_NOT_OK(PlanProjector(schema, exprs, mode, CodegenOptions::FromEnv(), &plan,
+                                    mode == SelectionMode::kNone ? 0x7fffffff : static_cast<int>(schema.size())));
   }
   std::unique_ptr<tier0::Args> prog(new tier0::Args);
   std::string why;

@@ -357,7 +357,8 @@ Status PrecompileProjector(const Schema& schema, const std::vector<ExpressionPtr
                            SelectionMode mode);
 Status PrecompileFilter(const Schema& schema, const ExpressionPtr& condition);
 // tier 0 (round 6): the post-fix program the interpreter kernel would run for these expressions / this condition
-Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exprs, bool is_condition, std::string* text);
+Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exprs, bool is_condition, std::string* text,
+                     SelectionMode mode = SelectionMode::kNone);
 Status PrecompileFilterProject(const Schema& schema, const ExpressionPtr& condition,
                                const std::vector<ExpressionPtr>& exprs, SelectionMode index_mode);
 

@@ -1,5 +1,7 @@
 #include "gdv_node.h"
 
+#include <algorithm>
+
 #include <cstdio>
 #include <cstring>
 #include <sstream>
@@ -319,6 +321,26 @@ NodePtr MakeFunctionNode(std::string name, NodeVector children, DataType ret) {
       PlainRegexLiteral(pat) && to.find('\\') == std::string::npos)
     return std::make_shared<FunctionNode>("replace", std::move(children), ret);
   return std::make_shared<FunctionNode>(std::move(name), std::move(children), ret);
+}
+
+std::vector<uint64_t> InListBitImages(const DataType& vt, const std::vector<Literal>& values) {
+  std::vector<uint64_t> vals;
+  const uint64_t mask = vt.byte_width() >= 8 ? ~0ull : ((1ull << (8 * vt.byte_width())) - 1);
+  const bool is_fp = vt.id == kFloat || vt.id == kDouble;
+  for (auto& l : values) {
+    uint64_t bits = l.lo & mask;
+    if (is_fp) {
+      const bool nan = vt.id == kFloat ? ((bits & 0x7f800000u) == 0x7f800000u && (bits & 0x7fffffu) != 0)
+                                       : ((bits & 0x7ff0000000000000ull) == 0x7ff0000000000000ull &&
+                                          (bits & 0xfffffffffffffull) != 0);
+      if (nan) continue;
+      if (bits == (vt.id == kFloat ? 0x80000000ull : 0x8000000000000000ull)) bits = 0;
+    }
+    vals.push_back(bits);
+  }
+  std::sort(vals.begin(), vals.end());
+  vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+  return vals;
 }
 
 }  // namespace gdv

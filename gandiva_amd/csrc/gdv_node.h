@@ -160,4 +160,8 @@ using ExpressionPtr = std::shared_ptr<Expression>;
 
 std::string LiteralToString(const DataType& t, const Literal& v);
 
+// The values of a fixed-width, non-decimal IN list as the kernels compare them: zero-extended bit images, sorted, without
+// duplicates.  Floats by value, as a hash set gives it: a NaN equals nothing (dropped), -0.0 is +0.0 (the probe adds +0.0).
+std::vector<uint64_t> InListBitImages(const DataType& value_type, const std::vector<Literal>& values);
+
 }  // namespace gdv

@@ -62,7 +62,7 @@ Status Projector::Make(const Schema& schema, const std::vector<ExpressionPtr>& e
   p->out_bytes_x16_ = std::vector<std::atomic<int64_t>>(exprs.size());
   const PlanDeviceState* st = nullptr;
   GDV_RETURN_NOT_OK(Runtime::Get().EnsureDevice());
-  if (p->pre_ == nullptr && mode == SelectionMode::kNone)
+  if (p->pre_ == nullptr)
     ArmTier0(schema, exprs, /*is_filter=*/false, p->plan_, &p->tier0_, &p->tier0_pending_);
   if (!p->tier0_) GDV_RETURN_NOT_OK(p->states_.Get(p->plan_, &st));  // compiles + loads on the calling thread's device
   ProjectorCache().Put(key, p);
@@ -296,7 +296,8 @@ Status Projector::Evaluate(int64_t num_rows, const ColumnBuffers* cols, int num_
   GDV_RETURN_NOT_OK(rt.EnsureDevice());
   const PlanDeviceState* dev = nullptr;
   // tier 0: while the specialised kernel is still compiling this evaluation interprets the plan's program instead
-  const bool tier0 = UseTier0() && !has_sel && rows_word == nullptr && err_word == nullptr;
+  // (row mode and selection mode alike; the asynchronous and gated paths — rows_word, err_word — stay on the specialised kernel)
+  const bool tier0 = UseTier0() && rows_word == nullptr && err_word == nullptr;
   GDV_RETURN_NOT_OK(states_.Get(plan_, &dev, /*need_kernel=*/!tier0));
 
   ArgBlock args(plan_.layout);

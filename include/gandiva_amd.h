@@ -634,8 +634,10 @@ int64_t gdv_device_pool_bytes(const gdv_device_pool_t* pool, int64_t* in_use);
 
 /* ---- tier 0 (round 6) ---------------------------------------------------------------
  * Make of an unseen tree used to wait for hipRTC (0.25-0.9 s; the reference's LLVM JIT takes tens of milliseconds).
- * Plans inside the fixed-width core — add / subtract / multiply, the six comparisons, not / isnull / isnotnull, the numeric
- * casts, if / else, AND / OR, literals, over bool / integer / float / date / time columns, row mode — now come with a
+ * Plans over the fixed-width registry — every function whose parameters and result are bool / integer / float / date /
+ * time, that cannot raise and is not a hash: arithmetic, comparisons, null handling (nvl, is_distinct_from, istrue ...),
+ * bitwise, the numeric and date casts, float64 math, the date / time functions, IN lists that fit the literal table,
+ * if / else, AND / OR, literals; row mode and, for projectors, selection mode — come with a
  * post-fix PROGRAM for an ahead-of-time interpreter kernel: gdv_projector_make / gdv_filter_make queue the compilation on a
  * background thread and return (milliseconds); evaluations interpret the program until the specialised code object
  * has arrived and then switch to it.  Same argument block, same device functions, same flags: results are
@@ -644,8 +646,11 @@ int64_t gdv_device_pool_bytes(const gdv_device_pool_t* pool, int64_t* in_use);
  * have a program always run on it: how the parity suite is held to tier 0).
  * gdv_tier0_program: the program of a projector's expressions (is_condition = 0) or a filter's condition (1) as text,
  * one instruction per line — or NULL, with the reason why the plan has no tier 0 in gdv_last_error().  No device needed.
+ * gdv_tier0_program_selection: the same for a projector built in a selection mode (0 none, 1 uint16, 2 uint32, 3 uint64
+ * indices); the text then starts with a "select uint<bits>" line.
  * gdv_tier0_launches: evaluations that ran on tier 0 so far (process-wide, cumulative). */
 char* gdv_tier0_program(const gdv_schema_t* schema, gdv_expression_t* const* exprs, int num_exprs, int is_condition);
+char* gdv_tier0_program_selection(const gdv_schema_t* schema, gdv_expression_t* const* exprs, int num_exprs, int selection_mode);
 int64_t gdv_tier0_launches(void);
 /* Stops the background compiler: queued compilations are dropped, the one in flight is waited for (<= ~1 s).  The library
  * does this itself when the process exits through its MAIN thread and that thread has called a Make (a thread_local guard,
