@@ -347,11 +347,6 @@ struct ScratchPart {  // a piece of a scratch block, spelled like a DeviceBuffer
 };
 
 
-// bytes per element of a selection vector (kNone: no vector, 0)
-inline int IndexWidth(SelectionMode mode) {
-  return mode == SelectionMode::kUInt16 ? 2 : mode == SelectionMode::kUInt32 ? 4 : mode == SelectionMode::kUInt64 ? 8 : 0;
-}
-
 // ------------------------------------------------------------------ first-stage temporaries
 // (StageCapacity, the other half of the sizing, is in gdv_engine_policy.h)
 

@@ -20,6 +20,10 @@
 namespace gdv {
 
 enum class SelectionMode : int32_t { kNone = 0, kUInt16 = 1, kUInt32 = 2, kUInt64 = 3 };
+// bytes per element of a selection vector (kNone: no vector, 0)
+inline int IndexWidth(SelectionMode mode) {
+  return mode == SelectionMode::kUInt16 ? 2 : mode == SelectionMode::kUInt32 ? 4 : mode == SelectionMode::kUInt64 ? 8 : 0;
+}
 
 enum class KernelKind { kProject, kFilter, kFilterProject };
 

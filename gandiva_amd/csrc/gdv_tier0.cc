@@ -270,7 +270,7 @@ bool BuildTier0Program(const Schema& schema, const std::vector<ExpressionPtr>& e
   out->n_in = plan.layout.n_in;
   out->filter = filter ? 1 : 0;
   out->subtiles = plan.opts.subtiles;
-  out->selw = plan.mode == SelectionMode::kUInt16 ? 2 : plan.mode == SelectionMode::kUInt32 ? 4 : plan.mode == SelectionMode::kUInt64 ? 8 : 0;
+  out->selw = IndexWidth(plan.mode);
   for (size_t e = 0; e < exprs.size(); e++) {
     const Node& root = *exprs[e]->root();
     if (!b.Node(root)) return fail("");
