@@ -130,3 +130,143 @@ def _mask(rng, n, null_fraction):
     if null_fraction >= 1:
         return np.ones(n, dtype=bool)
     return rng.random(n) < null_fraction
+
+
+def py_murmur3_x64_128_h1(data: bytes, seed: int) -> int:
+    """Independent pure-Python MurmurHash3_x64_128, first 64 bits (signed)."""
+    M = (1 << 64) - 1
+    c1, c2 = 0x87c37b91114253d5, 0x4cf5ad432745937f
+    rotl = lambda v, d: ((v << d) | (v >> (64 - d))) & M
+
+    def fmix(k):
+        k ^= k >> 33; k = k * 0xff51afd7ed558ccd & M; k ^= k >> 33
+        k = k * 0xc4ceb9fe1a85ec53 & M; k ^= k >> 33
+        return k
+    h1 = h2 = seed & M
+    nblocks = len(data) // 16
+    for b in range(nblocks):
+        k1 = int.from_bytes(data[16 * b: 16 * b + 8], "little")
+        k2 = int.from_bytes(data[16 * b + 8: 16 * b + 16], "little")
+        k1 = k1 * c1 & M; k1 = rotl(k1, 31); k1 = k1 * c2 & M; h1 ^= k1
+        h1 = rotl(h1, 27); h1 = (h1 + h2) & M; h1 = (h1 * 5 + 0x52dce729) & M
+        k2 = k2 * c2 & M; k2 = rotl(k2, 33); k2 = k2 * c1 & M; h2 ^= k2
+        h2 = rotl(h2, 31); h2 = (h2 + h1) & M; h2 = (h2 * 5 + 0x38495ab5) & M
+    tail = data[16 * nblocks:]
+    if len(tail) > 8:
+        k2 = int.from_bytes(tail[8:], "little")
+        k2 = k2 * c2 & M; k2 = rotl(k2, 33); k2 = k2 * c1 & M; h2 ^= k2
+    if tail:
+        k1 = int.from_bytes(tail[:8], "little")
+        k1 = k1 * c1 & M; k1 = rotl(k1, 31); k1 = k1 * c2 & M; h1 ^= k1
+    h1 ^= len(data); h2 ^= len(data)
+    h1 = (h1 + h2) & M; h2 = (h2 + h1) & M
+    h1, h2 = fmix(h1), fmix(h2)
+    h1 = (h1 + h2) & M
+    return h1 - (1 << 64) if h1 >> 63 else h1
+
+
+# ---- full-range operands (tests/test_full_range_numeric*.py) ----------------------------------------------------------
+
+def _np_dtype(t):
+    return np.dtype(t.to_pandas_dtype())
+
+
+def edge_values(t):
+    """The values of numeric type t at which magnitude-dependent code goes wrong, most important first, deduplicated.
+
+    Integers of width w (a Python list, clipped to the type): min, min+1, max-1, max, -1, 0, 1, 2; +-2^(w/2) and its two
+    neighbours; for unsigned types the values on either side of 2^(w-1); where they fit, the integers that a conversion
+    to float must round (2^24 + 1, 2^24 + 3, 2^53 + 1, 2^53 + 3, and 2^54 + 2^30 + 1, which rounds the other way when
+    it is rounded to float64 first and to float32 after); then 2^k and 2^k - 1 for every k < w.
+    Floats (a numpy array): +-0, the smallest and largest denormal, the smallest normal, 1, 1 +- 1 ulp, 0.5 - 1 ulp, max,
+    inf, one NaN, then 2^24, 2^24 + 1, 2^53, 2^53 + 1 (each as the type rounds it), 2147483647.5, 2^31, 2^63 and its
+    lower neighbour, all with both signs."""
+    if pa.types.is_integer(t):
+        w = t.bit_width
+        signed = pa.types.is_signed_integer(t)
+        lo, hi = (-(1 << (w - 1)), (1 << (w - 1)) - 1) if signed else (0, (1 << w) - 1)
+        h = 1 << (w // 2)
+        vals = [lo, lo + 1, hi - 1, hi, -1, 0, 1, 2, h - 1, h, h + 1, -h + 1, -h, -h - 1]
+        if not signed:
+            vals += [(1 << (w - 1)) - 1, 1 << (w - 1), (1 << (w - 1)) + 1]
+        round_me = [(1 << 24) + 1, (1 << 24) + 3, (1 << 53) + 1, (1 << 53) + 3, (1 << 54) + (1 << 30) + 1]
+        vals += [s * v for v in round_me if v <= hi for s in (1, -1)]
+        for k in range(w):
+            vals += [1 << k, (1 << k) - 1]
+        out = []
+        for v in vals:
+            v = min(max(v, lo), hi)
+            if v not in out:
+                out.append(v)
+        return out
+    dt = np.float32 if pa.types.is_float32(t) else np.float64
+    fi = np.finfo(dt)
+    one = dt(1.0)
+    with np.errstate(over="ignore"):
+        pos = [dt(0.0), fi.smallest_subnormal, np.nextafter(fi.tiny, dt(0.0)), fi.tiny, one, np.nextafter(one, dt(2.0)),
+               np.nextafter(one, dt(0.0)), np.nextafter(dt(0.5), dt(0.0)), fi.max, dt(np.inf),
+               dt(2.0 ** 24), dt(2.0 ** 24 + 1), dt(2.0 ** 53), dt(np.float64(2 ** 53 + 2) if dt is np.float64 else 2.0 ** 53),
+               dt(2147483647.5), dt(2.0 ** 31), dt(2.0 ** 63), np.nextafter(dt(2.0 ** 63), dt(0.0))]
+    out, seen = [], set()
+    for i, v in enumerate(pos):
+        for s in (v, -v):
+            bits = np.array([s], dtype=dt).tobytes()
+            if bits not in seen:
+                seen.add(bits)
+                out.append(s)
+        if i == 9:
+            out.append(dt(np.nan))
+    return np.array(out, dtype=dt)
+
+
+def full_range_values(rng, t, n):
+    """n values of numeric type t (numpy) in which every magnitude is equally likely: integers are uniformly random bit
+    images shifted right by a random 0..w-1 (arithmetically for signed types: the sign is kept); floats are uniformly
+    random bit images (exponent-uniform, denormals included) with NaN images thinned to at most 1 % of the rows."""
+    dt = _np_dtype(t)
+    w = t.bit_width
+    raw = rng.integers(0, 1 << 64, n, dtype=np.uint64) >> np.uint64(64 - w)
+    if pa.types.is_integer(t):
+        vals = raw.astype({8: np.uint8, 16: np.uint16, 32: np.uint32, 64: np.uint64}[w]).view(dt)
+        return vals >> rng.integers(0, w, n).astype(dt)
+    vals = raw.astype(np.uint32 if w == 32 else np.uint64).view(dt)
+    surplus = np.flatnonzero(np.isnan(vals))[n // 100:]
+    bits = vals.view(np.uint32 if w == 32 else np.uint64)
+    bits[surplus] &= ~(bits.dtype.type(1) << bits.dtype.type(w - 2))     # the exponent's top bit cleared: finite
+    return vals
+
+
+def full_range_array(rng, t, n, null_fraction=0.1):
+    """full_range_values as a pyarrow array with a random validity bitmap."""
+    return pa.array(full_range_values(rng, t, n), type=t, mask=_mask(rng, n, null_fraction))
+
+
+def nonzero_divisors(vals):
+    """A divisor column: 0 becomes 1 and +-0.0 becomes +-1.0 (that x / 0 raises is pinned elsewhere); nothing else changes."""
+    vals = vals.copy()
+    if vals.dtype.kind == "f":
+        zero = vals == 0
+        vals[zero] = np.copysign(vals.dtype.type(1), vals[zero])
+    else:
+        vals[vals == 0] = 1
+    return vals
+
+
+def edge_pair_values(rng, t, n=4099, cross=32):
+    """Two operand columns (numpy) of n rows: the first k * k rows are the cross product E x E of the first k = min(cross,
+    len(E)) edge values of t, random full-range rows follow, and every third of those carries a value of the whole edge
+    list in its first, its second or both columns (lists longer than `cross` are covered that way).  4099 rows hold the
+    cross product of 32 values and about 3000 random rows."""
+    dt = _np_dtype(t)
+    edges = np.array(edge_values(t), dtype=dt)
+    k = min(cross, len(edges))
+    assert k * k < n
+    a, b = full_range_values(rng, t, n), full_range_values(rng, t, n)
+    a[:k * k] = np.repeat(edges[:k], k)
+    b[:k * k] = np.tile(edges[:k], k)
+    rows = np.arange(k * k, n, 3)
+    which = rng.integers(0, 3, len(rows))
+    ea, eb = edges[rng.integers(0, len(edges), len(rows))], edges[rng.integers(0, len(edges), len(rows))]
+    a[rows[which != 1]] = ea[which != 1]
+    b[rows[which != 0]] = eb[which != 0]
+    return a, b

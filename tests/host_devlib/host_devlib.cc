@@ -554,4 +554,139 @@ void host_months_between(const long long* s, const long long* e, long n, int uni
                        : timestampdiffYear_timestamp_timestamp(s[i], e[i]);
 }
 
+// ---------------------------------------------------------------- the numeric core on full-range operands
+// (tests/test_full_range_numeric_cpu.py).  tk: 0 int8, 1 int16, 2 int32, 3 int64, 4 uint8, 5 uint16, 6 uint32, 7 uint64,
+// 8 float32, 9 float64.  Divisors are never 0 (the raising path is tested elsewhere); the error word is dropped.
+#define HOST_EACH_INT(X) X(0, int8) X(1, int16) X(2, int32) X(3, int64) X(4, uint8) X(5, uint16) X(6, uint32) X(7, uint64)
+#define HOST_EACH_NUMERIC(X) HOST_EACH_INT(X) X(8, float32) X(9, float64)
+// op: 0 add, 1 subtract, 2 multiply, 3 divide
+void host_int_binary(int tk, int op, const void* av, const void* bv, void* outv, long n) {
+  unsigned err = 0;
+  gdv_ctx ctx{&err};
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                          \
+  case K: {                                                                                              \
+    const gdv_##T a = ((const gdv_##T*)av)[i], b = ((const gdv_##T*)bv)[i];                              \
+    ((gdv_##T*)outv)[i] = op == 0 ? add_##T##_##T(a, b) : op == 1 ? subtract_##T##_##T(a, b)             \
+                        : op == 2 ? multiply_##T##_##T(a, b) : divide_##T##_##T(ctx, a, b);              \
+    break;                                                                                               \
+  }
+      HOST_EACH_INT(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// tk: 0 float32, 1 float64; op as host_int_binary
+void host_float_binary(int tk, int op, const void* av, const void* bv, void* outv, long n) {
+  unsigned err = 0;
+  gdv_ctx ctx{&err};
+  for (long i = 0; i < n; i++) {
+    if (tk == 0) {
+      const gdv_float32 a = ((const gdv_float32*)av)[i], b = ((const gdv_float32*)bv)[i];
+      ((gdv_float32*)outv)[i] = op == 0 ? add_float32_float32(a, b) : op == 1 ? subtract_float32_float32(a, b)
+                              : op == 2 ? multiply_float32_float32(a, b) : divide_float32_float32(ctx, a, b);
+    } else {
+      const gdv_float64 a = ((const gdv_float64*)av)[i], b = ((const gdv_float64*)bv)[i];
+      ((gdv_float64*)outv)[i] = op == 0 ? add_float64_float64(a, b) : op == 1 ? subtract_float64_float64(a, b)
+                              : op == 2 ? multiply_float64_float64(a, b) : divide_float64_float64(ctx, a, b);
+    }
+  }
+}
+// op: 0 equal, 1 not_equal, 2 less_than, 3 less_than_or_equal_to, 4 greater_than, 5 greater_than_or_equal_to
+void host_compare(int tk, int op, const void* av, const void* bv, unsigned char* out, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                          \
+  case K: {                                                                                              \
+    const gdv_##T a = ((const gdv_##T*)av)[i], b = ((const gdv_##T*)bv)[i];                              \
+    out[i] = op == 0 ? equal_##T##_##T(a, b) : op == 1 ? not_equal_##T##_##T(a, b)                       \
+           : op == 2 ? less_than_##T##_##T(a, b) : op == 3 ? less_than_or_equal_to_##T##_##T(a, b)       \
+           : op == 4 ? greater_than_##T##_##T(a, b) : greater_than_or_equal_to_##T##_##T(a, b);          \
+    break;                                                                                               \
+  }
+      HOST_EACH_NUMERIC(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// sig: 0 mod(int64, int32) -> int32, 1 mod(int64, int64) -> int64, 2 mod(int32, int32) -> int32
+void host_mod(int sig, const void* av, const void* bv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (sig) {
+      case 0: ((gdv_int32*)outv)[i] = mod_int64_int32(((const gdv_int64*)av)[i], ((const gdv_int32*)bv)[i]); break;
+      case 1: ((gdv_int64*)outv)[i] = mod_int64_int64(((const gdv_int64*)av)[i], ((const gdv_int64*)bv)[i]); break;
+      default: ((gdv_int32*)outv)[i] = mod_int32_int32(((const gdv_int32*)av)[i], ((const gdv_int32*)bv)[i]); break;
+    }
+  }
+}
+// op: 0 castBIGINT(int32), 1 castINT(int64), 2 castFLOAT4(int32), 3 castFLOAT4(int64), 4 castFLOAT4(float64),
+//     5 castFLOAT8(int32), 6 castFLOAT8(int64), 7 castFLOAT8(float32), 8 castBIGINT(float32), 9 castBIGINT(float64),
+//     10 castINT(float32), 11 castINT(float64)
+void host_cast(int op, const void* xv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (op) {
+      case 0: ((gdv_int64*)outv)[i] = castBIGINT_int32(((const gdv_int32*)xv)[i]); break;
+      case 1: ((gdv_int32*)outv)[i] = castINT_int64(((const gdv_int64*)xv)[i]); break;
+      case 2: ((gdv_float32*)outv)[i] = castFLOAT4_int32(((const gdv_int32*)xv)[i]); break;
+      case 3: ((gdv_float32*)outv)[i] = castFLOAT4_int64(((const gdv_int64*)xv)[i]); break;
+      case 4: ((gdv_float32*)outv)[i] = castFLOAT4_float64(((const gdv_float64*)xv)[i]); break;
+      case 5: ((gdv_float64*)outv)[i] = castFLOAT8_int32(((const gdv_int32*)xv)[i]); break;
+      case 6: ((gdv_float64*)outv)[i] = castFLOAT8_int64(((const gdv_int64*)xv)[i]); break;
+      case 7: ((gdv_float64*)outv)[i] = castFLOAT8_float32(((const gdv_float32*)xv)[i]); break;
+      case 8: ((gdv_int64*)outv)[i] = castBIGINT_float32(((const gdv_float32*)xv)[i]); break;
+      case 9: ((gdv_int64*)outv)[i] = castBIGINT_float64(((const gdv_float64*)xv)[i]); break;
+      case 10: ((gdv_int32*)outv)[i] = castINT_float32(((const gdv_float32*)xv)[i]); break;
+      default: ((gdv_int32*)outv)[i] = castINT_float64(((const gdv_float64*)xv)[i]); break;
+    }
+  }
+}
+// tk: 0 int32, 1 int64, 2 float32, 3 float64
+#define HOST_EACH_MINMAX(X) X(0, int32) X(1, int64) X(2, float32) X(3, float64)
+// op: 0 greatest, 1 least
+void host_minmax(int tk, int op, const void* av, const void* bv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                          \
+  case K: {                                                                                              \
+    const gdv_##T a = ((const gdv_##T*)av)[i], b = ((const gdv_##T*)bv)[i];                              \
+    ((gdv_##T*)outv)[i] = op == 0 ? greatest_##T##_##T(a, b) : least_##T##_##T(a, b);                    \
+    break;                                                                                               \
+  }
+      HOST_EACH_MINMAX(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// op: 0 negative, 1 abs
+void host_unary(int tk, int op, const void* xv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                          \
+  case K: ((gdv_##T*)outv)[i] = op == 0 ? negative_##T(((const gdv_##T*)xv)[i]) : abs_##T(((const gdv_##T*)xv)[i]); break;
+      HOST_EACH_MINMAX(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// hash32 (wide = 0, int32 results) / hash64 (wide = 1, int64 results) of valid values of any numeric type, seed 0
+void host_hash_numeric(int tk, int wide, const void* xv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                          \
+  case K:                                                                                                \
+    if (wide) ((gdv_int64*)outv)[i] = hash64_##T(((const gdv_##T*)xv)[i], true);                         \
+    else ((gdv_int32*)outv)[i] = hash32_##T(((const gdv_##T*)xv)[i], true);                              \
+    break;
+      HOST_EACH_NUMERIC(X)
+#undef X
+      default: break;
+    }
+  }
+}
+
 }  // extern "C"

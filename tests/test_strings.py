@@ -205,37 +205,7 @@ def test_hip_c5_matches_oracle_host_and_device_paths(nulls):
 
 # ------------------------------------------------------------------ hash over var-len values
 
-def _py_murmur3_x64_128_h1(data: bytes, seed: int) -> int:
-    """Independent pure-Python MurmurHash3_x64_128, first 64 bits (signed)."""
-    M = (1 << 64) - 1
-    c1, c2 = 0x87c37b91114253d5, 0x4cf5ad432745937f
-    rotl = lambda v, d: ((v << d) | (v >> (64 - d))) & M
-
-    def fmix(k):
-        k ^= k >> 33; k = k * 0xff51afd7ed558ccd & M; k ^= k >> 33
-        k = k * 0xc4ceb9fe1a85ec53 & M; k ^= k >> 33
-        return k
-    h1 = h2 = seed & M
-    nblocks = len(data) // 16
-    for b in range(nblocks):
-        k1 = int.from_bytes(data[16 * b: 16 * b + 8], "little")
-        k2 = int.from_bytes(data[16 * b + 8: 16 * b + 16], "little")
-        k1 = k1 * c1 & M; k1 = rotl(k1, 31); k1 = k1 * c2 & M; h1 ^= k1
-        h1 = rotl(h1, 27); h1 = (h1 + h2) & M; h1 = (h1 * 5 + 0x52dce729) & M
-        k2 = k2 * c2 & M; k2 = rotl(k2, 33); k2 = k2 * c1 & M; h2 ^= k2
-        h2 = rotl(h2, 31); h2 = (h2 + h1) & M; h2 = (h2 * 5 + 0x38495ab5) & M
-    tail = data[16 * nblocks:]
-    if len(tail) > 8:
-        k2 = int.from_bytes(tail[8:], "little")
-        k2 = k2 * c2 & M; k2 = rotl(k2, 33); k2 = k2 * c1 & M; h2 ^= k2
-    if tail:
-        k1 = int.from_bytes(tail[:8], "little")
-        k1 = k1 * c1 & M; k1 = rotl(k1, 31); k1 = k1 * c2 & M; h1 ^= k1
-    h1 ^= len(data); h2 ^= len(data)
-    h1 = (h1 + h2) & M; h2 = (h2 + h1) & M
-    h1, h2 = fmix(h1), fmix(h2)
-    h1 = (h1 + h2) & M
-    return h1 - (1 << 64) if h1 >> 63 else h1
+from helpers import py_murmur3_x64_128_h1 as _py_murmur3_x64_128_h1  # noqa: E402  (imported from here by other test files)
 
 
 def _hash_exprs(b, s, k):
