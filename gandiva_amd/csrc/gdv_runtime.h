@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "gdv_reclaim.h"
 #include "gdv_types.h"
 
 namespace gdv {
@@ -136,11 +137,19 @@ class Runtime {
   std::map<std::string, std::unique_ptr<CompiledKernel>> kernels_;
   std::multimap<size_t, void*> free_blocks_;
   std::map<void*, size_t> live_blocks_;
-  std::vector<char*> pinned_free_, pinned_small_free_;
-  std::vector<hipStream_t> streams_free_;
-  std::vector<hipEvent_t> events_free_;
-  std::vector<std::pair<hipEvent_t, void*>> deferred_;  // FreeAfter: blocks waiting for their event
-  std::vector<std::pair<hipEvent_t, std::function<void()>>> deferred_fns_;
+  bool TakeFree(size_t sz, void** ptr);  // a free block of exactly `sz` bytes, moved to live_blocks_
+  // The pools and the deferred work have mutexes of their own (gdv_reclaim.h); mu_ guards the rest: the probe, kernels_,
+  // the block maps, all_ones_.
+  FreeList<char*> pinned_{8, [](char* p) { (void)hipHostFree(p); }};
+  FreeList<char*> pinned_small_{256, [](char* p) { (void)hipHostFree(p); }};
+  FreeList<hipStream_t> streams_{16, [](hipStream_t s) { (void)hipStreamDestroy(s); }};
+  FreeList<hipEvent_t> events_{64, [](hipEvent_t e) { (void)hipEventDestroy(e); }};
+  Status AcquirePinnedOf(FreeList<char*>& pool, size_t bytes, const char* what, char** p);
+  // FreeAfter and Defer: work waiting for its event, tagged with the block's rounded size (0: not a block)
+  using Deferred = DeferredQueue<hipEvent_t>;
+  Deferred deferred_;
+  void Defer(hipStream_t stream, size_t tag, std::function<void()> fn);
+  void Complete(Deferred::Entry& d, bool wait);  // the caller took `d` out of deferred_: it alone owns the event
   void Reap(bool wait);
   size_t cached_bytes_ = 0;
   uint64_t* all_ones_ = nullptr;

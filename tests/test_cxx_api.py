@@ -33,7 +33,7 @@ def test_cxx_api_reference_kats_on_gpu():
 def test_a_cxx_process_that_ends_while_its_kernels_are_still_compiling_exits_cleanly(tmp_path):
     """Round 6: with an EMPTY code-object cache the program above finishes on tier 0 within a second of its first Make — and
     then crashed or hung in exit(): the compiler's function-local statics, registered during the compilation in flight, were
-    torn down under the worker thread.  The main thread's thread_local guard (gdv_runtime.cc) joins the worker first."""
+    torn down under the worker thread.  The main thread's thread_local guard (gdv_code_cache.cc) joins the worker first."""
     _build()
     for attempt in range(3):
         cache = tmp_path / f"cache{attempt}"
