@@ -405,6 +405,21 @@ Status CodeGen::GenCall(const FunctionNode& fn, const FunctionDef& def, FnArgs& 
     push("ctx");
     can_raise_ = true;
   }
+  // functions that see validity: value, (precision, scale) of a decimal, validity; the result's pair when it is a decimal
+  auto push_with_validity = [&](const Val& a) {
+    push(a.v);
+    if ((def.flags & kDecimalArgs) && a.type.is_decimal()) {
+      push(std::to_string(a.type.precision));
+      push(std::to_string(a.type.scale));
+    }
+    push(LaneValid(a));
+  };
+  auto push_decimal_result = [&]() {
+    if ((def.flags & kDecimalArgs) && out->type.is_decimal()) {
+      push(std::to_string(out->type.precision));
+      push(std::to_string(out->type.scale));
+    }
+  };
   if (def.policy == NullPolicy::kNullIfNull) {
     for (auto& a : args) {
       push(a.v);
@@ -430,17 +445,13 @@ Status CodeGen::GenCall(const FunctionNode& fn, const FunctionDef& def, FnArgs& 
       out->v = Tmp(ctype, call);
     }
   } else if (def.policy == NullPolicy::kNullNever) {
-    for (auto& a : args) {
-      push(a.v);
-      push(LaneValid(a));
-    }
+    for (auto& a : args) push_with_validity(a);
+    push_decimal_result();
     call += ")";
     out->v = Tmp(ctype, call);
   } else {
-    for (auto& a : args) {
-      push(a.v);
-      push(LaneValid(a));
-    }
+    for (auto& a : args) push_with_validity(a);
+    push_decimal_result();
     std::string ov = "ov" + std::to_string(next_tmp_++);
     Stmt("bool " + ov + " = false;");
     push("&" + ov);

@@ -1106,6 +1106,74 @@ GDV_DEV gdv_float64 castFLOAT8_decimal128(gdv_int128 x, int xp, int xs, int op, 
 GDV_DEV gdv_int64 castBIGINT_decimal128(gdv_int128 x, int xp, int xs, int op, int os) {
   return (gdv_int64)gdv_dec_reduce(x, xs);
 }
+// ---- decimal tail: casts from floats, the cast that answers NULL on overflow, nvl / greatest / least and the null-safe
+// comparisons.  (castDECIMAL of text sits next to castBIGINT_utf8, the hashes behind GDV_HASH_BUF.)
+// the double nearest to 10^k, k in [0, 38]: the literals, so host and device compilers agree on every one
+GDV_DEV gdv_float64 gdv_dec_pow10_f64(int k) {
+  const gdv_float64 t[39] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11, 1e12,
+                             1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22, 1e23, 1e24, 1e25,
+                             1e26, 1e27, 1e28, 1e29, 1e30, 1e31, 1e32, 1e33, 1e34, 1e35, 1e36, 1e37, 1e38};
+  return t[k < 0 ? 0 : (k > 38 ? 38 : k)];
+}
+// float64 -> decimal(op, os) [recalled: the lineage's FromDouble]: u = x * 10^os in ONE IEEE multiplication, rounded to an
+// integer half away from zero; NaN or |r| >= 10^op: 0, like every decimal overflow here.  The integer-valued double is split
+// into two 64-bit halves (exact: it has at most 53 significant bits), never cast to a 64-bit integer as a whole.
+GDV_DEV gdv_int128 castDECIMAL_float64(gdv_float64 x, int op, int os) {
+  const gdv_float64 u = x * gdv_dec_pow10_f64(os);
+  if (u != u) return 0;
+  gdv_float64 t = trunc(u);
+  if (fabs(u - t) >= 0.5) t += u < 0 ? -1.0 : 1.0;  // (|u| + 0.5 would round 0.49999999999999994 up)
+  const gdv_float64 a = fabs(t);
+  if (!(a < 170141183460469231731687303715884105728.0)) return 0;  // 2^127 > 10^38; +-inf ends here
+  const gdv_uint64 hi = (gdv_uint64)(a * 5.421010862427522170037264004349708557128906250e-20);  // a / 2^64, truncated
+  const gdv_uint64 lo = (gdv_uint64)(a - (gdv_float64)hi * 18446744073709551616.0);
+  const gdv_uint128 mag = ((gdv_uint128)hi << 64) | lo;
+  if (mag >= (gdv_uint128)gdv_pow10_128(op)) return 0;
+  return t < 0 ? -(gdv_int128)mag : (gdv_int128)mag;
+}
+GDV_DEV gdv_int128 castDECIMAL_float32(gdv_float32 x, int op, int os) { return castDECIMAL_float64((gdv_float64)x, op, os); }
+// castDECIMAL_decimal128 with NULL instead of 0 where the value does not fit the declared precision (0 is a value)
+GDV_DEV gdv_int128 castDECIMALNullOnOverflow_decimal128(gdv_int128 x, int xp, int xs, bool xv, int op, int os, bool* out_valid) {
+  *out_valid = false;
+  if (!xv) return 0;
+  gdv_int128 r;
+  if (os >= xs) {
+    const int by = os - xs;
+    if (x != 0) {
+      if (op - by <= 0) return 0;
+      const gdv_int128 lim_in = gdv_pow10_128(op - by);
+      if (x >= lim_in || x <= -lim_in) return 0;
+    }
+    r = x * gdv_pow10_128(by);
+  } else {
+    r = gdv_dec_reduce(x, xs - os);
+    const gdv_int128 lim = gdv_pow10_128(op);
+    if (r >= lim || r <= -lim) return 0;
+  }
+  *out_valid = true;
+  return r;
+}
+// nvl / greatest / least: both sides and the result have one (precision, scale) (checked at Make): plain 128-bit integers
+GDV_DEV gdv_int128 nvl_decimal128_decimal128(gdv_int128 a, int ap, int asc, bool av, gdv_int128 b, int bp, int bs, bool bv,
+                                             int op, int os, bool* out_valid) {
+  *out_valid = av || bv;
+  return av ? a : b;
+}
+GDV_DEV gdv_int128 greatest_decimal128_decimal128(gdv_int128 x, int xp, int xs, gdv_int128 y, int yp, int ys, int op, int os) {
+  return x > y ? x : y;
+}
+GDV_DEV gdv_int128 least_decimal128_decimal128(gdv_int128 x, int xp, int xs, gdv_int128 y, int yp, int ys, int op, int os) {
+  return x < y ? x : y;
+}
+// by VALUE over any two (precision, scale): 1.0 and 1 are not distinct (the generic template compares bit images)
+GDV_DEV bool is_distinct_from_decimal128_decimal128(gdv_int128 x, int xp, int xs, bool xv, gdv_int128 y, int yp, int ys, bool yv) {
+  if (xv != yv) return true;
+  if (!xv) return false;
+  return gdv_dec_compare(x, xp, xs, y, yp, ys) != 0;
+}
+GDV_DEV bool is_not_distinct_from_decimal128_decimal128(gdv_int128 x, int xp, int xs, bool xv, gdv_int128 y, int yp, int ys, bool yv) {
+  return !is_distinct_from_decimal128_decimal128(x, xp, xs, xv, y, yp, ys, yv);
+}
 
 // ------------------------------------------------------------------ utf8 / binary
 // A string value inside a kernel is a VIEW: pointer + byte length into an input data buffer
@@ -2002,6 +2070,26 @@ GDV_DEV gdv_int32 gdv_murmur3_32_buf(const gdv_str& s, gdv_int32 seed) {
   }
 GDV_HASH_BUF(utf8)
 GDV_HASH_BUF(binary)
+// decimal128: MurmurHash3 over the 16 little-endian bytes of the value, as over a binary of that length; a NULL hashes to
+// the seed (0 without one).  The two words are read back 8 bytes at a time: the loops above have a known trip count.
+GDV_DEV gdv_int32 gdv_dec_hash32(gdv_int128 v, gdv_int32 seed) {
+  const gdv_uint64 w[2] = {(gdv_uint64)v, (gdv_uint64)((gdv_uint128)v >> 64)};
+  return gdv_murmur3_32_buf(gdv_make_str((const gdv_uint8*)w, 0, 16, (const gdv_uint8*)(w + 2), GDV_STR_INBUF), seed);
+}
+GDV_DEV gdv_int64 gdv_dec_hash64(gdv_int128 v, gdv_int32 seed) {
+  const gdv_uint64 w[2] = {(gdv_uint64)v, (gdv_uint64)((gdv_uint128)v >> 64)};
+  return gdv_murmur3_64_buf(gdv_make_str((const gdv_uint8*)w, 0, 16, (const gdv_uint8*)(w + 2), GDV_STR_INBUF), seed);
+}
+GDV_DEV gdv_int32 hash32_decimal128(gdv_int128 v, int vp, int vs, bool valid) { return valid ? gdv_dec_hash32(v, 0) : 0; }
+GDV_DEV gdv_int32 hash32_decimal128_int32(gdv_int128 v, int vp, int vs, bool valid, gdv_int32 seed, bool sv) {
+  const gdv_int32 s = sv ? seed : 0;
+  return valid ? gdv_dec_hash32(v, s) : s;
+}
+GDV_DEV gdv_int64 hash64_decimal128(gdv_int128 v, int vp, int vs, bool valid) { return valid ? gdv_dec_hash64(v, 0) : 0; }
+GDV_DEV gdv_int64 hash64_decimal128_int64(gdv_int128 v, int vp, int vs, bool valid, gdv_int64 seed, bool sv) {
+  const gdv_int64 s = sv ? seed : 0;
+  return valid ? gdv_dec_hash64(v, (gdv_int32)s) : s;
+}
 
 GDV_DEV gdv_int32 octet_length_utf8(gdv_str s) { return s.len; }
 GDV_DEV gdv_int32 bit_length_utf8(gdv_str s) { return s.len * 8; }
@@ -2822,6 +2910,76 @@ GDV_DEV gdv_int32 castINT_utf8(gdv_ctx ctx, gdv_str s) {
     return 0;
   }
   return (gdv_int32)v;
+}
+// castDECIMAL from text: [+-]? ( D+ ( '.' D* )? | '.' D+ ) ( [eE] [+-]? D+ )? over ASCII digits, nothing trimmed — the accept
+// set of arrow::Decimal128::FromString, the parser the lineage calls; decided here: an exponent of more than 9 digits and a
+// second sign in it ("1e+-5") are refused.  The value is the EXACT decimal value of the text rounded half away from zero to
+// `os` fractional digits; more than `op` digits: 0, no error.  128-bit arithmetic, whatever the text's length: a first walk
+// checks the grammar and finds the exponent (so a bad byte raises wherever it stands), a second one accumulates the digits
+// of weight >= 10^-os; the first dropped digit alone decides the rounding (half-away ties round up).
+GDV_DEV bool gdv_parse_decimal(const gdv_str& s, int op, int os, gdv_int128* out) {
+  const gdv_int32 n = s.len;
+  gdv_int32 i = 0;
+  bool neg = false;
+  if (i < n && (gdv_str_at(s, i) == '+' || gdv_str_at(s, i) == '-')) { neg = gdv_str_at(s, i) == '-'; i++; }
+  const gdv_int32 int_begin = i;
+  while (i < n && (gdv_uint8)(gdv_str_at(s, i) - '0') <= 9) i++;
+  const gdv_int32 int_end = i;
+  gdv_int32 frac_begin = i, frac_end = i;
+  if (i < n && gdv_str_at(s, i) == '.') {
+    i++;
+    frac_begin = i;
+    while (i < n && (gdv_uint8)(gdv_str_at(s, i) - '0') <= 9) i++;
+    frac_end = i;
+  }
+  if (int_end == int_begin && frac_end == frac_begin) return false;  // no digit: "", ".", "+", ".e5"
+  gdv_int64 exp10 = 0;
+  if (i < n && (gdv_str_at(s, i) | 0x20) == 'e') {
+    i++;
+    bool eneg = false;
+    if (i < n && (gdv_str_at(s, i) == '+' || gdv_str_at(s, i) == '-')) { eneg = gdv_str_at(s, i) == '-'; i++; }
+    const gdv_int32 e_begin = i;
+    while (i < n && (gdv_uint8)(gdv_str_at(s, i) - '0') <= 9) { exp10 = exp10 * 10 + (gdv_str_at(s, i) - '0'); i++; if (i - e_begin > 9) return false; }
+    if (i == e_begin) return false;
+    if (eneg) exp10 = -exp10;
+  }
+  if (i != n) return false;
+  // digit k of the run (integer digits, then fraction digits) has weight 10^(int_digits - 1 - k + exp10)
+  const gdv_int64 int_digits = int_end - int_begin;
+  const gdv_int32 total = (int_end - int_begin) + (frac_end - frac_begin);
+  const gdv_uint128 top = (gdv_uint128)gdv_pow10_128(37);
+  gdv_uint128 acc = 0;  // < 10^38 throughout
+  bool over = false;
+  gdv_int64 w = int_digits - 1 + exp10;  // weight of the digit at hand
+  for (gdv_int32 k = 0; k < total; k++, w--) {
+    if (w < -(gdv_int64)os - 1) break;  // below the rounding digit: cannot change the result
+    const gdv_int32 at = k < int_end - int_begin ? int_begin + k : frac_begin + (k - (int_end - int_begin));
+    const gdv_uint32 d = (gdv_uint32)(gdv_str_at(s, at) - '0');
+    if (w == -(gdv_int64)os - 1) {
+      if (d >= 5 && !over) acc += 1;
+      break;
+    }
+    if (acc >= top) over = true;  // one more digit makes 39
+    if (!over) acc = acc * 10 + d;
+  }
+  // digits end above 10^-os ("12e3" at scale 2): the zeros that follow
+  const gdv_int64 last_w = int_digits - (gdv_int64)total + exp10;  // weight of the last digit
+  gdv_int128 r = 0;
+  if (!over && acc != 0) {
+    const gdv_int64 by = last_w + os > 0 ? last_w + os : 0;
+    if (by > op || acc >= (gdv_uint128)gdv_pow10_128(op - (int)by)) over = true;
+    else r = (gdv_int128)(acc * (gdv_uint128)gdv_pow10_128((int)by));
+  }
+  *out = over ? (gdv_int128)0 : (neg ? -r : r);
+  return true;
+}
+GDV_DEV gdv_int128 castDECIMAL_utf8(gdv_ctx ctx, gdv_str s, int op, int os) {
+  gdv_int128 v = 0;
+  if (!gdv_parse_decimal(s, op, os, &v)) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    return 0;
+  }
+  return v;
 }
 // ascii(s): the first byte as a signed char (0 for the empty string)
 GDV_DEV gdv_int32 ascii_utf8(gdv_str s) { return s.len > 0 ? (gdv_int32)(gdv_int8)gdv_str_at(s, 0) : 0; }

@@ -56,6 +56,13 @@ Status ValidateFunction(const Schema& schema, const FunctionNode& n) {
                                      n.return_type().ToString());
     }
   }
+  if (def->flags & kSameDecimalType) {  // nvl / greatest / least over decimals: the value is one of the arguments, as it is
+    for (auto& c : n.children()) {
+      if (c->return_type() != n.return_type())
+        return Status::ValidationError("Function " + n.name() + " takes decimal arguments of the result's precision and scale: " +
+                                       c->return_type().ToString() + " given, " + n.return_type().ToString() + " declared");
+    }
+  }
   if (def->flags & kPatternArg) {
     if (n.children().size() < 2 || n.children()[1]->kind() != NodeKind::kLiteral) {
       return Status::ValidationError("'" + n.name() + "' function requires a literal as the last parameter");

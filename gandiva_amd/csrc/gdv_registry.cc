@@ -283,6 +283,23 @@ FunctionRegistry::FunctionRegistry() {
     add("castVARCHAR", {dec, int64()}, utf8(), NullPolicy::kNullIfNull, kDecimalArgs | kVarlenResult | kNeedsContext);
     add("isnull", {dec}, boolean(), NullPolicy::kNullNever, 0, "gdv_isnull");
     add("isnotnull", {dec}, boolean(), NullPolicy::kNullNever, 0, "gdv_isnotnull");
+    // decimal tail: casts from floats and text (the text parser raises on what it does not take), the cast that answers
+    // NULL where castDECIMAL answers 0, nvl / greatest / least over ONE decimal type (gdv_plan_validate.cc), the null-safe
+    // comparisons by value and the hash family over the value's 16 bytes (no ...AsDouble names: PARITY.md, decimal tail)
+    add("castDECIMAL", {float64()}, dec, NullPolicy::kNullIfNull, kDecimalArgs);
+    add("castDECIMAL", {float32()}, dec, NullPolicy::kNullIfNull, kDecimalArgs);
+    add("castDECIMAL", {utf8()}, dec, NullPolicy::kNullIfNull, kDecimalArgs | kNeedsContext);
+    add("castDECIMALNullOnOverflow", {dec}, dec, NullPolicy::kNullInternal, kDecimalArgs);
+    add("nvl", {dec, dec}, dec, NullPolicy::kNullInternal, kDecimalArgs | kSameDecimalType);
+    add("greatest", {dec, dec}, dec, NullPolicy::kNullIfNull, kDecimalArgs | kSameDecimalType);
+    add("least", {dec, dec}, dec, NullPolicy::kNullIfNull, kDecimalArgs | kSameDecimalType);
+    add("is_distinct_from", {dec, dec}, boolean(), NullPolicy::kNullNever, kDecimalArgs);
+    add("is_not_distinct_from", {dec, dec}, boolean(), NullPolicy::kNullNever, kDecimalArgs);
+    add("hash", {dec}, int32(), NullPolicy::kNullNever, kDecimalArgs, Sym("hash32", {dec}));
+    add("hash32", {dec}, int32(), NullPolicy::kNullNever, kDecimalArgs);
+    add("hash64", {dec}, int64(), NullPolicy::kNullNever, kDecimalArgs);
+    add("hash32", {dec, int32()}, int32(), NullPolicy::kNullNever, kDecimalArgs);
+    add("hash64", {dec, int64()}, int64(), NullPolicy::kNullNever, kDecimalArgs);
   }
   // utf8 / binary
   for (auto& t : {utf8(), binary()}) {

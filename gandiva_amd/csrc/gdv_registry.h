@@ -26,7 +26,9 @@ enum FunctionFlags : uint32_t {
   kPatternArg = 4u,      // last argument must be a literal compiled at Make time (like)
   kVarlenResult = 8u,    // returns utf8/binary: two-pass (length, then copy) evaluation
   kDecimalArgs = 16u,    // device function takes (precision, scale) after every decimal
-                         // argument and the result's (precision, scale) last
+                         // argument and the result's (precision, scale) last (never-null and
+                         // null-internal functions: the result's only when it is a decimal)
+  kSameDecimalType = 64u,  // decimal parameters and result share one (precision, scale): checked at Make
   kDateFormatArg = 32u,  // to_date: the pattern (and suppress_errors) must be literals; compiled at Make time
 };
 
