@@ -279,6 +279,19 @@ int gdv_compile_regex(const char* pattern, int64_t pattern_len, uint8_t* table) 
   });
 }
 
+int gdv_compile_regex_extract(const char* pattern, int64_t pattern_len, int32_t group, uint8_t* table, int64_t cap, int64_t* n) {
+  return Guarded([&]() -> int {
+  if (!pattern || pattern_len < 0 || !table || !n) return Fail(Status::Invalid("null argument"));
+  std::string bytes;
+  Status st = CompileRegexExtract(std::string(pattern, static_cast<size_t>(pattern_len)), group, &bytes);
+  if (!st.ok()) return Fail(st);
+  if (static_cast<int64_t>(bytes.size()) > cap) return Fail(Status::Invalid("table buffer too small"));
+  std::memcpy(table, bytes.data(), bytes.size());
+  *n = static_cast<int64_t>(bytes.size());
+  return 0;
+  });
+}
+
 int gdv_compile_date_format(const char* pattern, int64_t pattern_len, uint8_t* ops, int64_t cap, int64_t* n) {
   return Guarded([&]() -> int {
   if (!pattern || pattern_len < 0 || !ops || !n) return Fail(Status::Invalid("null argument"));

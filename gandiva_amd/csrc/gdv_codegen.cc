@@ -197,6 +197,7 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       out->type = fn.return_type();
       const std::string& name = fn.name();
       if (name == "regexp_like" || name == "regexp_matches") return GenRegexpLike(fn, args, active, out);
+      if (name == "regexp_extract") return GenRegexpExtract(fn, args, active, out);
       if (name.compare(0, 7, "regexp_") == 0)
         return Status::CodeGenError("Function " + fn.ToString() + " not supported yet: the HIP backend takes regexp_replace "
                                     "with a literal pattern and a replacement without backslashes only (no metacharacters, "

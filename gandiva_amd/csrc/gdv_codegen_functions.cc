@@ -159,6 +159,27 @@ Status CodeGen::GenRegexpLike(const FunctionNode& fn, FnArgs& args, const std::s
   return Status::OK();
 }
 
+Status CodeGen::GenRegexpExtract(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out) {
+  // regexp_extract(text, 'pattern', index) with a LITERAL pattern and index: the ordered lists for that one group are built
+  // here, once per expression, into the constant block; the row's value is a narrower view of its text (as split_part's is)
+  if (fn.children()[1]->kind() != NodeKind::kLiteral || fn.children()[2]->kind() != NodeKind::kLiteral)
+    return Status::CodeGenError("Function " + fn.ToString() + " not supported yet: the HIP backend takes regexp_extract "
+                                "with a literal pattern and a literal group index only (the pattern is compiled for that "
+                                "group when the expression is compiled). ");
+  auto& pat = static_cast<const LiteralNode&>(*fn.children()[1]);
+  auto& idx = static_cast<const LiteralNode&>(*fn.children()[2]);
+  out->vcols = args[0].vcols;
+  if (pat.is_null() || idx.is_null()) return NullString(out);
+  if (!args[0].pieces.empty() || args[0].opaque)
+    return Status::CodeGenError("Function " + fn.ToString() + " not supported yet: a concat / lpad / rpad / reverse / replace / "
+                                "castVARCHAR(number) result can only be an output expression or an argument of concat in the HIP backend. ");
+  std::string table;
+  GDV_RETURN_NOT_OK(CompileRegexExtract(pat.value().bytes, static_cast<int32_t>(idx.value().lo), &table));
+  out->vlane = args[0].vlane;
+  out->v = Tmp("gdv_str", "gdv_regex_extract(" + args[0].v + ", " + ByteTable(table) + ")");
+  return Status::OK();
+}
+
 Status CodeGen::GenReplace(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out) {
   // replace(text, from, to) with LITERAL from / to: a table in the constant block; the result
   // is materialised by the output copy (GDV_MAP_REPLACE)

@@ -2469,6 +2469,90 @@ GDV_DEV bool gdv_regex_search(const gdv_str& s, const gdv_uint8* table) {
   }
   return false;
 }
+// ---- regexp_extract(text, 'pattern', index): group `index` of the FIRST match RE2's unanchored search takes, as a narrower
+// view of the text ("" without a match or when the group took no part).  The planner lays the pattern out as lists of ways
+// in order of preference (gdv_regex.h, CompileRegexExtract): list p holds what may come behind position p, list 63 what may
+// begin a match; a way = target (63: the match ends) | predicates of the gap << 6 | what happens to the group << 10.  The
+// row keeps its live positions in that order, each with the extents of the group so far.  Over the gap in front of byte i
+// every live position, most preferred first, offers its ways: a way whose predicates hold and whose target accepts the byte
+// enters the next list unless a preferred one entered that target already; a way that ends the match records it and drops
+// everything less preferred, the rest of its own list included.  While nothing has matched a new attempt joins at the end of
+// the order (a later start is less preferred than any earlier one).  No backtracking: at most 63 entries per byte, each
+// scanning one list.  The gap's predicates and the rule inside a multi-byte character are gdv_regex_search's: an attempt may
+// begin there ("not a word boundary"), one under way passes no assertion there — and does not end there.
+// Private state: the two lists (64 positions, 64 + 64 extents each: 1152 bytes of scratch per lane), nothing sized by the text.
+GDV_DEV gdv_str gdv_regex_extract(gdv_str s, const gdv_uint8* table) {
+  // the screen: regexp_like's table and walk (one 64-bit set per byte) come first; a row without a match is done
+  if (!gdv_regex_search(s, table)) {
+    s.len = 0;
+    return s;
+  }
+  table += 6352;  // GDV_REGEX_TABLE_BYTES
+  const gdv_uint64* t = (const gdv_uint64*)table;
+  const bool start_only = (t[0] & 1) != 0;
+  const gdv_uint64* match = t + 1;
+  const gdv_uint64* targets = t + 257;
+  const gdv_uint16* first = (const gdv_uint16*)(table + 2568);
+  const gdv_uint16* ways = (const gdv_uint16*)(table + 2704);
+  const gdv_int32 len = s.len > 0 ? s.len : 0;
+  gdv_uint8 at[2][64];
+  gdv_int32 from[2][64], to[2][64];
+  gdv_int32 n = 0, cur = 0, found_from = -1, found_to = -1;
+  bool found = false, prev_word = false;
+  for (gdv_int32 i = 0; i <= len; i++) {
+    const gdv_uint8 b = i < len ? gdv_str_at(s, i) : (gdv_uint8)0;
+    const bool next_word = i < len && gdv_regex_word_byte(b);
+    const bool inside = i < len && (b & 0xC0) == 0x80;
+    const gdv_uint32 gap = (prev_word != next_word ? 1u : 2u) | (i == 0 ? 4u : 0u) | (i == len ? 8u : 0u);
+    const gdv_uint32 run = inside ? 0u : gap;  // what a match under way may ask of this gap
+    const gdv_uint64 fits = i < len ? match[b] : 0ull;
+    const gdv_int32 nx = cur ^ 1;
+    gdv_uint64 entered = 0;
+    gdv_int32 m = 0;
+    bool cut = false;
+    // the live positions, then (k == n) a new attempt
+    for (gdv_int32 k = 0; k <= n && !cut; k++) {
+      const bool fresh = k == n;
+      if (fresh && found) break;
+      const gdv_int32 p = fresh ? 63 : (gdv_int32)at[cur][k];
+      const gdv_uint32 may = fresh ? gap : run;
+      const bool may_end = fresh || !inside;
+      if ((targets[p] & ((fits & ~entered) | (may_end ? 1ull << 63 : 0ull))) == 0) continue;
+      const gdv_int32 f0 = fresh ? -1 : from[cur][k], t0 = fresh ? -1 : to[cur][k];
+      for (gdv_int32 e = first[p], e1 = first[p + 1]; e < e1; e++) {
+        const gdv_uint32 w = ways[e];
+        if ((((w >> 6) & 15u) & ~may) != 0) continue;
+        const gdv_uint32 q = w & 63u, act = w >> 10;
+        if (q != 63u && (((fits & ~entered) >> q) & 1ull) == 0) continue;
+        if (q == 63u && !may_end) continue;
+        const gdv_int32 f1 = act >= 2u ? i : f0;
+        const gdv_int32 t1 = act == 2u ? -1 : act != 0u ? i : t0;
+        if (q == 63u) {
+          found = cut = true;
+          found_from = f1;
+          found_to = t1;
+          break;
+        }
+        entered |= 1ull << q;
+        at[nx][m] = (gdv_uint8)q;
+        from[nx][m] = f1;
+        to[nx][m] = t1;
+        m++;
+      }
+    }
+    n = m;
+    cur = nx;
+    if (n == 0 && (found || start_only)) break;  // settled, or nothing can begin behind the first gap
+    prev_word = next_word;
+  }
+  if (found && found_from >= 0 && found_to >= found_from) {
+    s.p += found_from;
+    s.len = found_to - found_from;
+  } else {
+    s.len = 0;
+  }
+  return s;
+}
 // ---- to_date(text, 'pattern'[, suppress_errors]) (round 5).  The lineage's ToDateHolder turns the SQL pattern into a
 // strptime format at Make time (date_utils.cc ToInternalFormat) and calls arrow::internal::ParseTimestampStrptime(...,
 // ignore_time_in_day = true, allow_trailing_chars = true): the C library's strptime, then year / month / max(day, 1)

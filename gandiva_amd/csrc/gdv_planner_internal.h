@@ -89,6 +89,7 @@ class CodeGen {
   // specially planned functions, one emitter each (gdv_codegen_functions.cc); GenCall: everything else (the registry's symbol)
   using FnArgs = std::vector<Val>;
   Status GenRegexpLike(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
+  Status GenRegexpExtract(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenReplace(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenTranslate(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenPad(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);

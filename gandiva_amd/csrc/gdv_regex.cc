@@ -7,6 +7,8 @@
 #include <cstring>
 #include <initializer_list>
 #include <memory>
+#include <set>
+#include <utility>
 #include <vector>
 
 namespace gdv {
@@ -16,11 +18,15 @@ using ByteSet = std::bitset<256>;
 
 // syntax tree: leaves are byte sets (one automaton position each)
 struct Re {
-  enum Kind { kEmpty, kSet, kCat, kAlt, kStar, kPlus, kOpt, kAssert } kind = kEmpty;
+  enum Kind { kEmpty, kSet, kCat, kAlt, kStar, kPlus, kOpt, kAssert, kGroup } kind = kEmpty;
   int cond = 0;  // kAssert: 1 word boundary, 2 not a word boundary, 3 start of the text, 4 end of the text
   ByteSet set;
   std::unique_ptr<Re> a, b;
   int pos = -1;
+  // regexp_extract only (the parser's capture mode): a quantifier that prefers the shorter match; kGroup: the number of
+  // the capturing group around `a`
+  bool lazy = false;
+  int group = 0;
 };
 using ReP = std::unique_ptr<Re>;
 
@@ -48,6 +54,8 @@ ReP Clone(const Re& x) {
   r->kind = x.kind;
   r->set = x.set;
   r->cond = x.cond;
+  r->lazy = x.lazy;
+  r->group = x.group;
   if (x.a) r->a = Clone(*x.a);
   if (x.b) r->b = Clone(*x.b);
   return r;
@@ -128,7 +136,10 @@ constexpr int kMaxAtoms = 512;
 
 class Parser {
  public:
-  Parser(const std::string& p, bool fold, bool dot_nl) : p_(p), fold_(fold), dot_nl_(dot_nl) {}
+  // capture: keep what regexp_extract needs and "is there a match" does not — group nodes, lazy quantifiers, and counted
+  // repetitions nested the way RE2 nests them (x{2,4} = xx(x(x)?)?)
+  Parser(const std::string& p, bool fold, bool dot_nl, bool capture = false) : p_(p), fold_(fold), dot_nl_(dot_nl), capture_(capture) {}
+  int groups() const { return groups_; }
   Status Parse(ReP* out) {
     if (p_.size() > kMaxPatternBytes)
       return Status::CodeGenError("regular expression of " + std::to_string(p_.size()) + " bytes not supported by the HIP backend: longer than " +
@@ -180,6 +191,7 @@ class Parser {
         i_++;
         if (++atoms_ > kMaxAtoms) return Bad("more than " + std::to_string(kMaxAtoms) + " atoms and quantifiers");
         atom = Mk(c == '*' ? Re::kStar : c == '+' ? Re::kPlus : Re::kOpt, std::move(atom));
+        atom->lazy = capture_ && More() && p_[i_] == '?';
       } else if (c == '{') {
         size_t j = i_ + 1;
         auto number = [&](int* v) {
@@ -207,8 +219,19 @@ class Parser {
         ReP seq = Mk(Re::kEmpty);
         auto append = [&](ReP x) { seq = seq->kind == Re::kEmpty ? std::move(x) : Mk(Re::kCat, std::move(seq), std::move(x)); };
         for (int k = 0; k < lo; k++) append(Clone(*atom));
-        if (hi < 0) append(Mk(Re::kStar, Clone(*atom)));
-        for (int k = lo; k < hi; k++) append(Mk(Re::kOpt, Clone(*atom)));
+        if (capture_) {
+          const bool lazy = More() && p_[i_] == '?';
+          ReP tail;
+          if (hi < 0) tail = Mk(Re::kStar, Clone(*atom));
+          for (int k = lo; k < hi; k++) {
+            tail = Mk(Re::kOpt, tail ? Mk(Re::kCat, Clone(*atom), std::move(tail)) : Clone(*atom));
+            tail->lazy = lazy;
+          }
+          if (tail) { tail->lazy = lazy; append(std::move(tail)); }
+        } else {
+          if (hi < 0) append(Mk(Re::kStar, Clone(*atom)));
+          for (int k = lo; k < hi; k++) append(Mk(Re::kOpt, Clone(*atom)));
+        }
         atom = std::move(seq);
       } else {
         break;
@@ -352,9 +375,11 @@ class Parser {
       case '(': {
         i_++;
         if (depth_ >= kMaxNesting) return Bad("groups nested deeper than " + std::to_string(kMaxNesting));
+        bool capturing = true;
         if (More() && p_[i_] == '?') {
           if (i_ + 1 < p_.size() && p_[i_ + 1] == ':') {
             i_ += 2;
+            capturing = false;
           } else if (i_ + 2 < p_.size() && p_[i_ + 1] == 'P' && p_[i_ + 2] == '<') {  // (?P<name>...): a group like any other
             size_t j = i_ + 3;
             while (j < p_.size() && (std::isalnum(static_cast<unsigned char>(p_[j])) || p_[j] == '_')) j++;
@@ -364,11 +389,16 @@ class Parser {
             return Bad("group flags inside the pattern / look-around");
           }
         }
+        const int group = capturing ? ++groups_ : 0;  // numbered by opening parenthesis
         depth_++;
         GDV_RETURN_NOT_OK(Alt(out));
         depth_--;
         if (!More() || p_[i_] != ')') return Bad("unmatched '('");
         i_++;
+        if (capture_ && capturing) {
+          *out = Mk(Re::kGroup, std::move(*out));
+          (*out)->group = group;
+        }
         return Status::OK();
       }
       case '[':
@@ -428,9 +458,10 @@ class Parser {
   const std::string& p_;
   size_t i_ = 0;
   bool negated_escape_ = false;
-  int depth_ = 0, atoms_ = 0;
+  int depth_ = 0, atoms_ = 0, groups_ = 0;
   bool fold_ = false;    // (?i): ASCII letters match in either case
   bool dot_nl_ = false;  // (?s): '.' matches a newline too
+  bool capture_ = false;
 };
 
 // Position automaton with GAP CONDITIONS.  An assertion (^ $ \\A \\z \\b \\B) consumes nothing: it constrains the gap between two
@@ -514,6 +545,8 @@ struct Glushkov {
         if (x.kind != Re::kPlus) r.nullable |= 1;
         return r;
       }
+      case Re::kGroup:  // (capture mode only: never built for this automaton)
+        return Build(*x.a);
     }
     return r;
   }
@@ -521,7 +554,10 @@ struct Glushkov {
 
 }  // namespace
 
-Status CompileRegex(const std::string& pattern, std::string* table) {
+namespace {
+
+// the pattern's tree; `groups` (capture mode, may be null): the number of capturing groups
+Status ParsePattern(const std::string& pattern, bool capture, ReP* tree, int* groups) {
   // flags, in front of everything only: (?i) ASCII letters in either case, (?s) '.' matches a newline
   std::string body = pattern;
   bool fold = false, dot_nl = false;
@@ -533,15 +569,23 @@ Status CompileRegex(const std::string& pattern, std::string* table) {
       body.erase(0, j + 1);
     }
   }
-  ReP tree;
-  Parser parser(body, fold, dot_nl);
-  Status st = parser.Parse(&tree);
+  Parser parser(body, fold, dot_nl, capture);
+  Status st = parser.Parse(tree);
   if (!st.ok()) {  // (messages quote the pattern as the caller wrote it)
     const std::string quoted = "'" + body + "'";
     const size_t at = st.msg.find(quoted);
     if (at != std::string::npos && body != pattern) st.msg.replace(at, quoted.size(), "'" + pattern + "'");
     return st;
   }
+  if (groups != nullptr) *groups = parser.groups();
+  return Status::OK();
+}
+
+}  // namespace
+
+Status CompileRegex(const std::string& pattern, std::string* table) {
+  ReP tree;
+  GDV_RETURN_NOT_OK(ParsePattern(pattern, false, &tree, nullptr));
   Glushkov g;
   const Glushkov::Info top = g.Build(*tree);
   const std::string prefix = "regular expression '" + pattern + "' not supported yet by the HIP backend: ";
@@ -579,6 +623,179 @@ Status CompileRegex(const std::string& pattern, std::string* table) {
       if (g.sets[p].test(static_cast<size_t>(b))) m |= 1ull << p;
     match[b] = m;
   }
+  return Status::OK();
+}
+
+// ---- regexp_extract: the same positions, ORDERED.  "Is there a match" needs sets; "which match, and where does group g lie
+// in it" needs RE2's preferences: the leftmost start, then the first alternative, the longer (greedy) or shorter (lazy)
+// repetition.  The tree becomes a small graph of the kind a backtracking-free simulation walks — a byte position, a fork that
+// prefers its first way out, an assertion, the target group's opening / closing, the end — and the ways from one position to
+// the next (or to the end) are listed in the order a depth-first walk that takes the preferred way first reaches them: the
+// first listed way that the gap allows and the byte fits is the one RE2 takes.  Each way carries the predicates the gap has
+// to satisfy (the four predicate bits themselves, not a condition id) and what it does to the
+// group: nothing, close it, open it (closing a previous iteration first), or open and close it on the spot.
+namespace {
+
+bool Nullable(const Re& x) {  // can match the empty text (under some condition on the gap)
+  switch (x.kind) {
+    case Re::kEmpty: case Re::kAssert: case Re::kStar: case Re::kOpt: return true;
+    case Re::kSet: return false;
+    case Re::kCat: return Nullable(*x.a) && Nullable(*x.b);
+    case Re::kAlt: return Nullable(*x.a) || Nullable(*x.b);
+    case Re::kPlus: case Re::kGroup: return Nullable(*x.a);
+  }
+  return false;
+}
+// A repetition without an upper bound whose body can match the empty text: RE2 stops such a loop by rules of its own
+// (an iteration that consumed nothing is not repeated, and its simplifier rewrites some of these first); which
+// iteration the group then keeps is not something the ordered lists can state.
+bool HasEmptyLoop(const Re& x) {
+  if ((x.kind == Re::kStar || x.kind == Re::kPlus) && Nullable(*x.a)) return true;
+  return (x.a && HasEmptyLoop(*x.a)) || (x.b && HasEmptyLoop(*x.b));
+}
+
+constexpr int kAccept = 63;        // the "position" that ends the match; also the index of the start list
+constexpr size_t kExtractMatchAt = 8, kExtractMaskAt = 8 + 256 * 8, kExtractOffAt = kExtractMaskAt + 64 * 8,
+                 kExtractEntriesAt = kExtractOffAt + 136, kExtractMaxBytes = 32768;
+
+struct Ordered {
+  enum Kind { kByte, kFork, kAssert, kOpen, kClose, kEnd };
+  struct Node { Kind kind; int a, b; unsigned pred; };
+  std::vector<Node> nodes;
+  ByteSet sets[64];
+  int npos = 0, target = 0;
+  bool overflow = false;
+
+  int Add(Kind k, int a = -1, int b = -1, unsigned pred = 0) {
+    nodes.push_back({k, a, b, pred});
+    return static_cast<int>(nodes.size()) - 1;
+  }
+  // the entry of x, given where the match goes on behind it
+  int Build(const Re& x, int next) {
+    switch (x.kind) {
+      case Re::kEmpty: return next;
+      case Re::kAssert: return Add(kAssert, next, -1, 1u << (x.cond - 1));
+      case Re::kSet: {
+        if (npos >= 63) { overflow = true; return next; }
+        sets[npos] = x.set;
+        return Add(kByte, next, npos++);
+      }
+      case Re::kCat: return Build(*x.a, Build(*x.b, next));
+      case Re::kAlt: {
+        const int a = Build(*x.a, next), b = Build(*x.b, next);
+        return Add(kFork, a, b);
+      }
+      case Re::kOpt: {
+        const int a = Build(*x.a, next);
+        return x.lazy ? Add(kFork, next, a) : Add(kFork, a, next);
+      }
+      case Re::kStar:
+      case Re::kPlus: {
+        const int loop = Add(kFork);
+        const int body = Build(*x.a, loop);
+        nodes[loop].a = x.lazy ? next : body;
+        nodes[loop].b = x.lazy ? body : next;
+        return x.kind == Re::kStar ? loop : body;
+      }
+      case Re::kGroup: {
+        if (x.group != target) return Build(*x.a, next);
+        const int close = Add(kClose, next);
+        const int body = Build(*x.a, close);
+        return Add(kOpen, body);
+      }
+    }
+    return next;
+  }
+  // the ordered ways from `node` on: (target position | kAccept) | predicates << 6 | group action << 10.  `consumed`: the
+  // walk starts behind a byte (the gap cannot be the start of the text).  A node reached again under the same predicates
+  // adds nothing: the earlier way is preferred and applies whenever this one does.
+  void Walk(int node, unsigned pred, unsigned act, bool consumed, std::set<std::pair<int, unsigned>>* seen, std::vector<uint16_t>* out) {
+    if (!seen->insert({node, pred}).second) return;
+    const Node& n = nodes[static_cast<size_t>(node)];
+    switch (n.kind) {
+      case kByte:
+        if ((pred & 8u) == 0) out->push_back(static_cast<uint16_t>(static_cast<unsigned>(n.b) | pred << 6 | act << 10));
+        return;
+      case kEnd:
+        out->push_back(static_cast<uint16_t>(static_cast<unsigned>(kAccept) | pred << 6 | act << 10));
+        return;
+      case kFork:
+        Walk(n.a, pred, act, consumed, seen, out);
+        Walk(n.b, pred, act, consumed, seen, out);
+        return;
+      case kAssert: {
+        const unsigned p = pred | n.pred;
+        if ((p & 3u) == 3u || (consumed && (p & 4u))) return;  // a boundary that is none; the start of the text behind a byte
+        Walk(n.a, p, act, consumed, seen, out);
+        return;
+      }
+      case kOpen: Walk(n.a, pred, 2u, consumed, seen, out); return;
+      case kClose: Walk(n.a, pred, act == 2u ? 3u : act == 3u ? 3u : 1u, consumed, seen, out); return;
+    }
+  }
+};
+
+}  // namespace
+
+Status CompileRegexExtract(const std::string& pattern, int group, std::string* table) {
+  ReP tree;
+  int groups = 0;
+  GDV_RETURN_NOT_OK(ParsePattern(pattern, true, &tree, &groups));
+  if (group < 0 || group > groups)
+    return Status::CodeGenError("regexp_extract: group index " + std::to_string(group) + " is outside the groups 0.." + std::to_string(groups) +
+                                " of the regular expression '" + pattern + "'");
+  const std::string prefix = "regular expression '" + pattern + "' not supported yet by the HIP backend: ";
+  if (HasEmptyLoop(*tree))
+    return Status::CodeGenError(prefix + "regexp_extract over a repetition (* + {m,}) whose body can match the empty text, such as (a*)* or (a|)+");
+  // in front of the ordered lists: the table of "is there a match at all" (CompileRegex), which the row walks first — one
+  // 64-bit set per byte — so that only rows that hold a match pay for the ordered walk
+  std::string screen;
+  GDV_RETURN_NOT_OK(CompileRegex(pattern, &screen));
+  ReP whole = Mk(Re::kGroup, std::move(tree));  // group 0: the match itself
+  Ordered g;
+  g.target = group;
+  const int end = g.Add(Ordered::kEnd);
+  const int start = g.Build(*whole, end);
+  if (g.overflow) return Status::CodeGenError(prefix + "more than 63 automaton positions");
+  // layout, behind the screen's kRegexTableWords words: uint64 flags (bit 0: every way in asks for the start of the text) | uint64 match[256] | uint64 targets[64] (bit q:
+  // list p leads to position q, bit 63: to the end; index 63 = the start list) | uint16 first[65] (list p = entries first[p] ..
+  // first[p + 1]) padded to 136 bytes | uint16 entries[]
+  std::vector<uint16_t> entries;
+  uint16_t first[65] = {};
+  uint64_t targets[64] = {};
+  std::vector<int> byte_node(64, -1);
+  for (size_t k = 0; k < g.nodes.size(); k++)
+    if (g.nodes[k].kind == Ordered::kByte) byte_node[static_cast<size_t>(g.nodes[k].b)] = static_cast<int>(k);
+  bool start_only = true;
+  for (int p = 0; p < 64; p++) {
+    first[p] = static_cast<uint16_t>(entries.size());
+    const int from = p == kAccept ? start : byte_node[static_cast<size_t>(p)] < 0 ? -1 : g.nodes[static_cast<size_t>(byte_node[static_cast<size_t>(p)])].a;
+    if (from < 0) continue;
+    std::set<std::pair<int, unsigned>> seen;
+    const size_t before = entries.size();
+    g.Walk(from, 0, 0, p != kAccept, &seen, &entries);
+    for (size_t k = before; k < entries.size(); k++) {
+      targets[p] |= 1ull << (entries[k] & 63u);
+      if (p == kAccept && ((entries[k] >> 6) & 4u) == 0) start_only = false;
+    }
+    if (screen.size() + kExtractEntriesAt + 2 * entries.size() > kExtractMaxBytes)
+      return Status::CodeGenError(prefix + "regexp_extract table beyond " + std::to_string(kExtractMaxBytes) + " bytes (too many ways between positions)");
+  }
+  first[64] = static_cast<uint16_t>(entries.size());
+  *table = screen;
+  table->append(kExtractEntriesAt + 2 * entries.size(), '\0');
+  char* tb = &(*table)[screen.size()];
+  const uint64_t flags = start_only ? 1u : 0u;
+  std::memcpy(tb, &flags, 8);
+  for (int b = 0; b < 256; b++) {
+    uint64_t m = 0;
+    for (int p = 0; p < g.npos; p++)
+      if (g.sets[p].test(static_cast<size_t>(b))) m |= 1ull << p;
+    std::memcpy(tb + kExtractMatchAt + 8 * b, &m, 8);
+  }
+  std::memcpy(tb + kExtractMaskAt, targets, sizeof targets);
+  std::memcpy(tb + kExtractOffAt, first, sizeof first);
+  if (!entries.empty()) std::memcpy(tb + kExtractEntriesAt, entries.data(), 2 * entries.size());
   return Status::OK();
 }
 

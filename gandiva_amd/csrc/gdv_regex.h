@@ -22,6 +22,24 @@
 // patterns beyond 4096 bytes, 64 levels of nesting or 512 atoms and quantifiers (the tree is walked recursively; patterns come from user SQL).
 // Texts that are not valid UTF-8: '.' and negated classes take "a lead byte and whatever continuation bytes follow" as one
 // character, which RE2 does not — the two agree on valid UTF-8 only.
+//
+// regexp_extract(text, 'pattern', index) asks more: WHICH match RE2's unanchored search takes (the leftmost start, then the
+// first alternative that leads to a match, greedy quantifiers as long and lazy ones as short as that allows) and where group
+// `index` lies in it.  CompileRegexExtract takes the same syntax and limits and lays the same positions out for a walk in
+// order of preference (the device function gdv_regex_extract: an ordered list of at most 63 live positions, each with the
+// extents of the ONE group asked for; no backtracking, nothing sized by the text):
+//     the 6352 bytes above | uint64 flags | uint64 match[256] | uint64 targets[64] | uint16 first[65] (padded to 136 bytes) | uint16 ways[]
+// (the table of "is there a match" in front: the row walks that first, with its one 64-bit set, and only a row that holds a
+// match walks the ordered lists).
+// List p (p < 63: behind position p; 63: into the pattern) = ways[first[p] .. first[p + 1]), most preferred first.  A way is
+// target | predicates << 6 | action << 10: the position entered next (63 = the match ends here, which holds its place in the
+// order like any other way), the predicates of the gap (1 word boundary, 2 not one, 4 start of the text, 8 end of it — all
+// must hold), and what crossing the gap does to the group: 0 nothing, 1 it closes, 2 it opens (a previous iteration closes
+// first), 3 it opens and closes on the spot.  targets[p] = the union of list p's targets (a filter); flags bit 0: every way
+// in asks for the start of the text.  Groups are numbered by opening parenthesis, (?: ) does not count, (?P<name> ) does; the
+// copies a counted repetition makes of a group are the same group (the last iteration is kept).  Refused on top of the list
+// above: a repetition without an upper bound whose body can match the empty text — (a*)*, (a|)+, (\b)* — where RE2 stops
+// the loop by rules the ordered lists cannot state; tables beyond 32768 bytes.
 #pragma once
 #include <string>
 
@@ -31,6 +49,10 @@ namespace gdv {
 
 // table = the bytes described above; CodeGenError with the reason otherwise
 Status CompileRegex(const std::string& pattern, std::string* table);
+
+// table = the ordered lists for group `group` (0 = the whole match); CodeGenError for what is refused and for a group
+// index outside 0 .. the pattern's number of groups
+Status CompileRegexExtract(const std::string& pattern, int group, std::string* table);
 
 // to_date's SQL pattern -> one byte per strptime directive, the program gdv_parse_date interprets (gdv_regex.cc)
 Status CompileDateFormat(const std::string& pattern, std::string* ops);

@@ -326,6 +326,10 @@ FunctionRegistry::FunctionRegistry() {
   add("regexp_like", {utf8(), utf8()}, boolean(), NullPolicy::kNullIfNull, kPatternArg, "gdv_regex_search");
   add("regexp_matches", {utf8(), utf8()}, boolean(), NullPolicy::kNullIfNull, kPatternArg, "gdv_regex_search");
   add("regexp_replace", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_regexp_unsupported");
+  // regexp_extract(text, 'pattern', index): group `index` (0 = the whole match) of the first match RE2's unanchored search
+  // takes, "" without one — a narrower view of the text, as split_part's result is.  Pattern and index are literals (checked
+  // at Make time with a CodeGenError, as translate's from / to are: no kPatternArg); planned by GenRegexpExtract.
+  add("regexp_extract", {utf8(), utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_regex_extract");
   // ilike (round 4): like without regard to the case of ASCII letters — both sides are read through the
   // lower-case byte map, so every fast path of like (prefix / suffix / equality / '%needle%' answered by
   // the byte sweep) serves it.  The lineage folds case through RE2 (Unicode simple folding); letters

@@ -671,9 +671,15 @@ int gdv_precompile_filter_project(const gdv_schema_t* schema, gdv_expression_t* 
  * pattern, or a to_date pattern, before building an expression around it; tests drive the device functions' host build with
  * the tables.  gdv_compile_regex: `table` receives GDV_REGEX_TABLE_BYTES bytes (flags, nullable, predicates[8], first[8], last[8],
  * follow[64][8], match[256] as 64-bit words: gandiva_amd/csrc/gdv_regex.h).  gdv_compile_date_format: `ops` (capacity `cap`) receives one byte per
- * strptime directive ('L' c for a literal byte), *n their number.  0 or a status code; gdv_last_error() has the reason. */
+ * strptime directive ('L' c for a literal byte), *n their number.  gdv_compile_regex_extract: the table regexp_extract(text,
+ * pattern, group) walks (ways between positions in RE2's order of preference, with what each does to group `group`; layout in
+ * gdv_regex.h) — at most GDV_REGEX_EXTRACT_TABLE_MAX_BYTES bytes into `table` (capacity `cap`), *n their number; a group
+ * index outside 0 .. the pattern's group count is an error that names both.  0 or a status code; gdv_last_error() has the
+ * reason. */
 #define GDV_REGEX_TABLE_BYTES 6352
+#define GDV_REGEX_EXTRACT_TABLE_MAX_BYTES 32768
 int gdv_compile_regex(const char* pattern, int64_t pattern_len, uint8_t* table);
+int gdv_compile_regex_extract(const char* pattern, int64_t pattern_len, int32_t group, uint8_t* table, int64_t cap, int64_t* n);
 int gdv_compile_date_format(const char* pattern, int64_t pattern_len, uint8_t* ops, int64_t cap, int64_t* n);
 /* Kernel identity (diagnostics, tests).  A fused kernel is named after a hash of its generated text
  * and of the device-library functions that text reaches — not of the whole library, so an edit of a

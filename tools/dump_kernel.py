@@ -1,7 +1,7 @@
 """Dev tool: print the generated HIP source of a workload's fused kernel and (optionally)
 cross-compile it for gfx950 and show resource usage + ISA histogram.  No GPU needed.
 
-  python tools/dump_kernel.py c2 [--isa]
+  python tools/dump_kernel.py c2 [--isa]        (c1 .. c5, fp, or rx / rl: regexp_extract / regexp_like over C5's column)
 """
 import ctypes as C
 import os
@@ -30,6 +30,20 @@ def plan_source(which):
         sh = gg._make_schema(W.c3_schema())
         cond = W.c3_condition()
         rc = lib.gdv_precompile_filter(sh, cond._h)
+    elif which in ("rx", "rl"):
+        # regexp_extract(s, '(\\w+)@(\\w+)', 2) / regexp_like with the same pattern over C5's column (profiles/regexp_extract.txt)
+        import pyarrow as pa
+        schema = W.c5_schema()
+        tb = g.TreeExprBuilder()
+        col, pat = tb.make_field(schema.field(0)), tb.make_literal("(\\w+)@(\\w+)", pa.string())
+        if which == "rx":
+            ex = [tb.make_expression(tb.make_function("regexp_extract", [col, pat, tb.make_literal(2, pa.int32())], pa.string()),
+                                     pa.field("o", pa.string()))]
+        else:
+            ex = [tb.make_expression(tb.make_function("regexp_like", [col, pat], pa.bool_()), pa.field("o", pa.bool_()))]
+        sh = gg._make_schema(schema)
+        arr = (C.c_void_p * len(ex))(*[e._h for e in ex])
+        rc = lib.gdv_precompile_projector(sh, arr, len(ex), 0)
     else:
         schema, exprs = {"c1": (W.c1_schema, W.c1_expressions), "c2": (W.c2_schema, W.c2_expressions),
                          "c4": (W.c4_schema, W.c4_expressions), "c5": (W.c5_schema, W.c5_expressions)}[which]
@@ -59,5 +73,5 @@ if __name__ == "__main__":
                 print(f"{v:6d} {k}")
             meta = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", p], capture_output=True, text=True).stdout
             for l in meta.splitlines():
-                if any(s in l for s in ("vgpr_count", "sgpr_count", "spill", "lds_size", "scratch", ".name:")):
+                if any(s in l for s in ("vgpr_count", "sgpr_count", "spill", "lds_size", "scratch", "private_segment_fixed_size", ".name:")):
                     print(l.strip())
