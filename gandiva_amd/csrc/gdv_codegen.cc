@@ -209,7 +209,10 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       if (name == "castVARCHAR" && (args[0].type.id == kDate32 || args[0].type.id == kDate64 ||
                                     args[0].type.id == kTimestamp || args[0].type.id == kTime32))
         datetime_ = true;  // (planned as an ordinary call; its value is a GDV_MAP_DATETIME)
-      if ((name == "upper" || name == "lower") && args.size() == 1 && args[0].col_slot >= 0) {
+      // (GDV_UTF8_CASE=1 at Make: a value of its own, whose length follows from the bytes — no byte map over the column's offsets)
+      const bool utf8_case = opts_.utf8_case && (name == "upper" || name == "lower") && args.size() == 1;
+      if (utf8_case) out->opaque = true;
+      if (!utf8_case && (name == "upper" || name == "lower") && args.size() == 1 && args[0].col_slot >= 0) {
         out->col_slot = args[0].col_slot;
         out->col_map = name == "upper" ? 1 : 2;
       }
@@ -226,6 +229,7 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
                                       "HIP backend. ");
       if (name == "replace") return GenReplace(fn, args, active, out);
       if (name == "translate") return GenTranslate(fn, args, active, out);
+      if (utf8_case) return GenUtf8Case(fn, args, active, out);
       if (name == "lpad" || name == "rpad") return GenPad(fn, args, active, out);
       if (is_concat) return GenConcat(fn, args, active, out);
       if (def->flags & kDateFormatArg) return GenToDate(fn, args, active, out);

@@ -6,6 +6,14 @@
 
 namespace gdv::planner {
 
+namespace {
+#include "gdv_utf8_case_table.inc"  // gdv_utf8_upper_table / gdv_utf8_lower_table (tools/gen_utf8_case_table.py)
+// what one direction may take of a plan's constant block
+constexpr size_t kUtf8CaseTableMaxBytes = 16384;
+static_assert(sizeof(gdv_utf8_upper_table) <= kUtf8CaseTableMaxBytes && sizeof(gdv_utf8_lower_table) <= kUtf8CaseTableMaxBytes,
+              "utf8 case table beyond its bound");
+}  // namespace
+
 // One row per function the planner treats differently from a plain registry call.  (hash*: digests exactly when they return
 // text, and castVARCHAR(non-string) is opaque: both by type, in CodeGen::Gen.)
 unsigned FnTraits(const std::string& name) {
@@ -262,6 +270,25 @@ Status CodeGen::GenTranslate(const FunctionNode& fn, FnArgs& args, const std::st
   translate_ = true;
   const std::string guard = AndExpr(AndExpr("live", active), LaneValid(*out));
   out->v = Tmp("gdv_str", guard + " ? gdv_translate(ctx, " + args[0].v + ", " + ByteTable(tab) + ") : gdv_empty_str()");
+  return Status::OK();
+}
+
+Status CodeGen::GenUtf8Case(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out) {
+  // upper / lower(text) under GDV_UTF8_CASE=1: utf8proc's simple case map, one table per direction and plan in the constant
+  // block (gdv_device_lib.hpp lays it out); the row computes the length and validates, the output copy writes
+  const int dir = fn.name() == "upper" ? 1 : 2;
+  auto it = case_tables_.find(dir);
+  if (it == case_tables_.end()) {
+    const std::string tab = dir == 1 ? std::string(reinterpret_cast<const char*>(gdv_utf8_upper_table), sizeof(gdv_utf8_upper_table))
+                                     : std::string(reinterpret_cast<const char*>(gdv_utf8_lower_table), sizeof(gdv_utf8_lower_table));
+    it = case_tables_.emplace(dir, ByteTable(tab)).first;
+  }
+  out->vcols = args[0].vcols;
+  out->vlane = args[0].vlane;
+  can_raise_ = true;
+  utf8_case_ = true;
+  const std::string guard = AndExpr(AndExpr("live", active), LaneValid(*out));
+  out->v = Tmp("gdv_str", guard + " ? gdv_utf8_case(ctx, " + args[0].v + ", " + it->second + ") : gdv_empty_str()");
   return Status::OK();
 }
 

@@ -3521,6 +3521,149 @@ GDV_DEV void gdv_str_copy_ext(gdv_uint8* dst, const gdv_str& s) {
   gdv_str_copy(dst, s);
 }
 
+// ------------------------------------------------------------------ upper / lower under GDV_UTF8_CASE=1 at Make: every character
+// through utf8proc's simple case map (tools/gen_utf8_case_table.py restates it from pyarrow into gdv_utf8_case_table.inc; the
+// planner lays the direction a plan needs into its constant block).  The table: int32 kind (1 upper, 2 lower), int32 n1, int32
+// offset of stage 2, int32 unused; 128 bytes, bit b = some code point of the 64-code-point block b of the BMP changes its UTF-8
+// length; n1 bytes of stage 1 (entry b = the stage-2 block of code points 64 b .., 0: none of them changes); stage 2, blocks of
+// 64 uint16 = (mapped - code point) mod 2^16, 0 = unchanged (a mapped code point stays in its 64 Ki plane).  A lookup is two
+// dependent loads, never a search; both stages of one direction are below 16 KiB and stay in the vector L1 / L2.
+// A value of its own kind, GDV_MAP_UTF8CASE, as translate's is: the row function walks the text, raises on text that is not
+// UTF-8 by translate's rule (gdv_utf8_char_len) and returns the result's length; the copy only writes.  p = the text, lead =
+// its length, lead_p = the table, flags keeps GDV_STR_INBUF.  Sequences that pass the structural rule but are not Unicode
+// (over-long forms, surrogates, above U+10FFFF) are copied unchanged.  Stretches without a byte >= 0x80 of a view readable with
+// raw 8-byte loads (GDV_STR_INBUF) are taken a word at a time in both passes: counted as they are, mapped with gdv_map8.
+// The length differs from the source's only at the length-changing code points (34 upper, 27 lower): the row function looks a
+// character up only when the 128-byte bitmap says its block holds one; four-byte characters never change length.
+// Plans that hold such a value copy through GDV_COPY_UTF8CASE around the entry point they would use without it.
+#define GDV_MAP_UTF8CASE 1048576
+#define GDV_COPY_UTF8CASE(dst, v, otherwise) \
+  do { if ((v).map & GDV_MAP_UTF8CASE) gdv_copy_utf8_case(dst, v); else otherwise; } while (0)
+// the code point of the well-formed character of cl >= 2 bytes at byte i of p (first byte c); 0 when it is not Unicode
+GDV_DEV gdv_uint32 gdv_utf8_decode(const gdv_uint8* p, gdv_int32 i, gdv_int32 cl, gdv_uint8 c) {
+  if (cl == 2) {
+    const gdv_uint32 cp = ((gdv_uint32)(c & 0x1F) << 6) | (p[i + 1] & 0x3F);
+    return cp < 0x80 ? 0u : cp;
+  }
+  if (cl == 3) {
+    const gdv_uint32 cp = ((gdv_uint32)(c & 0x0F) << 12) | ((gdv_uint32)(p[i + 1] & 0x3F) << 6) | (p[i + 2] & 0x3F);
+    return (cp < 0x800 || (cp >= 0xD800 && cp <= 0xDFFF)) ? 0u : cp;
+  }
+  const gdv_uint32 cp = ((gdv_uint32)(c & 0x07) << 18) | ((gdv_uint32)(p[i + 1] & 0x3F) << 12) | ((gdv_uint32)(p[i + 2] & 0x3F) << 6) |
+                        (p[i + 3] & 0x3F);
+  return (cp < 0x10000 || cp > 0x10FFFF) ? 0u : cp;
+}
+GDV_DEV gdv_int32 gdv_utf8_cp_len(gdv_uint32 cp) { return cp < 0x80 ? 1 : cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4; }
+// what cp maps to (cp itself when the map leaves it alone)
+GDV_DEV gdv_uint32 gdv_utf8_case_lookup(const gdv_uint8* tab, gdv_uint32 cp) {
+  const gdv_uint32 b = cp >> 6;
+  if (b >= (gdv_uint32)((const gdv_int32*)tab)[1]) return cp;
+  const gdv_uint32 blk = tab[16 + 128 + b];
+  if (blk == 0) return cp;
+  const gdv_uint32 d = ((const gdv_uint16*)(tab + ((const gdv_int32*)tab)[2]))[blk * 64 + (cp & 63)];
+  return (cp & 0xFFFF0000u) | ((cp + d) & 0xFFFFu);
+}
+GDV_DEV gdv_str gdv_utf8_case(gdv_ctx ctx, gdv_str s, const gdv_uint8* tab) {
+  if (s.len <= 0) return s;
+  const bool words = (s.flags & GDV_STR_INBUF) != 0;
+  const gdv_uint8* lenmap = tab + 16;
+  gdv_int64 out = s.len;
+  for (gdv_int32 i = 0; i < s.len;) {
+    if (words) {
+      const gdv_int32 r = s.len - i < 8 ? s.len - i : 8;
+      if ((gdv_load8_raw(s.p + i) & gdv_low_bytes_mask(r) & GDV_B80) == 0) {
+        i += r;
+        continue;
+      }
+    }
+    const gdv_uint8 c = s.p[i];
+    if (c < 0x80) {
+      i++;
+      continue;
+    }
+    const gdv_int32 cl = gdv_utf8_char_len(s.p, i, s.len);
+    if (cl == 0) {
+      gdv_raise(ctx, GDV_ERR_BAD_ARG);
+      s.len = 0;
+      return s;
+    }
+    if (cl < 4) {
+      const gdv_uint32 cp = gdv_utf8_decode(s.p, i, cl, c);
+      if (cp != 0 && ((lenmap[cp >> 9] >> ((cp >> 6) & 7)) & 1)) out += gdv_utf8_cp_len(gdv_utf8_case_lookup(tab, cp)) - cl;
+    }
+    i += cl;
+  }
+  if (out > 0x7fffffffll) {
+    gdv_raise(ctx, GDV_ERR_BAD_ARG);
+    s.len = 0;
+    return s;
+  }
+  s.lead = (gdv_uint64)s.len;
+  s.lead_p = tab;
+  s.flags &= GDV_STR_INBUF;
+  s.len = (gdv_int32)out;
+  s.map = (s.map & GDV_MAP_CASE) | GDV_MAP_UTF8CASE;
+  return s;
+}
+// (never writes more than the row function's length)
+template <typename P>
+GDV_DEV void gdv_copy_utf8_case(P dst, const gdv_str& s) {
+  const gdv_uint8* tab = s.lead_p;
+  const gdv_int32 dir = ((const gdv_int32*)tab)[0], len = (gdv_int32)s.lead, cm = s.map & GDV_MAP_CASE, cap = s.len;
+  const bool words = (s.flags & GDV_STR_INBUF) != 0;
+  gdv_int32 o = 0;
+  for (gdv_int32 i = 0; i < len;) {
+    if (words) {
+      const gdv_int32 r = len - i < 8 ? len - i : 8;
+      gdv_uint64 w = gdv_load8_raw(s.p + i);
+      if ((w & gdv_low_bytes_mask(r) & GDV_B80) == 0) {
+        if (o + r > cap) return;
+        w = gdv_map8(gdv_map8(w, cm), dir);
+        if (r == 8) __builtin_memcpy(dst + o, &w, 8); else gdv_store_low_bytes(dst + o, w, r);
+        o += r;
+        i += r;
+        continue;
+      }
+    }
+    const gdv_uint8 c = gdv_map_byte(s.p[i], cm);
+    if (c < 0x80) {
+      if (o >= cap) return;
+      dst[o++] = gdv_map_byte(c, dir);
+      i++;
+      continue;
+    }
+    const gdv_int32 cl = gdv_utf8_char_len(s.p, i, len);
+    if (cl == 0) return;  // (the row function raised: never reached with a length)
+    const gdv_uint32 cp = gdv_utf8_decode(s.p, i, cl, c);
+    const gdv_uint32 to = cp != 0 ? gdv_utf8_case_lookup(tab, cp) : 0u;
+    if (to == cp) {
+      if (o + cl > cap) return;
+      dst[o++] = c;
+      for (gdv_int32 j = 1; j < cl; j++) dst[o++] = s.p[i + j];
+    } else {
+      const gdv_int32 ol = gdv_utf8_cp_len(to);
+      if (o + ol > cap) return;
+      if (ol == 1) {
+        dst[o] = (gdv_uint8)to;
+      } else if (ol == 2) {
+        dst[o] = (gdv_uint8)(0xC0 | (to >> 6));
+        dst[o + 1] = (gdv_uint8)(0x80 | (to & 0x3F));
+      } else if (ol == 3) {
+        dst[o] = (gdv_uint8)(0xE0 | (to >> 12));
+        dst[o + 1] = (gdv_uint8)(0x80 | ((to >> 6) & 0x3F));
+        dst[o + 2] = (gdv_uint8)(0x80 | (to & 0x3F));
+      } else {
+        dst[o] = (gdv_uint8)(0xF0 | (to >> 18));
+        dst[o + 1] = (gdv_uint8)(0x80 | ((to >> 12) & 0x3F));
+        dst[o + 2] = (gdv_uint8)(0x80 | ((to >> 6) & 0x3F));
+        dst[o + 3] = (gdv_uint8)(0x80 | (to & 0x3F));
+      }
+      o += ol;
+    }
+    i += cl;
+  }
+}
+
 // ------------------------------------------------------------------ text <-> date / time: castDATE, castTIMESTAMP, castTIME
 // of text; castVARCHAR of date32, date64, timestamp, time32; castTIME(timestamp), castTIMESTAMP(date32).  Timestamps and times
 // are milliseconds.  Every function is null if null; a row that does not parse raises GDV_ERR_BAD_ARG.

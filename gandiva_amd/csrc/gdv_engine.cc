@@ -359,7 +359,7 @@ Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exp
                      SelectionMode mode) {
   KernelPlan plan;
   StagedExpressions staged;
-  StageMaterialisedValues(schema, exprs, &staged);
+  StageMaterialisedValues(schema, exprs, &staged, CodegenOptions::FromEnv());
   if (!staged.pre.empty()) return Status::NotImplemented("no tier 0: the plan materialises values in a first stage");
   if (is_condition) {
     if (exprs.size() != 1) return Status::Invalid("one condition expected");
@@ -382,7 +382,7 @@ Status PrecompileProjector(const Schema& schema, const std::vector<ExpressionPtr
                            SelectionMode mode) {
   KernelPlan plan;
   StagedExpressions staged;
-  StageMaterialisedValues(schema, exprs, &staged);
+  StageMaterialisedValues(schema, exprs, &staged, CodegenOptions::FromEnv());
   if (!staged.pre.empty()) {
     for (auto& e : exprs) GDV_RETURN_NOT_OK(ValidateExpression(schema, *e));
     GDV_RETURN_NOT_OK(PrecompileProjector(schema, staged.pre, mode));
@@ -412,7 +412,7 @@ Status PrecompileProjector(const Schema& schema, const std::vector<ExpressionPtr
 Status PrecompileFilter(const Schema& schema, const ExpressionPtr& condition) {
   KernelPlan plan;
   StagedExpressions staged;
-  StageMaterialisedValues(schema, {condition}, &staged);
+  StageMaterialisedValues(schema, {condition}, &staged, CodegenOptions::FromEnv());
   if (!staged.pre.empty()) {
     GDV_RETURN_NOT_OK(ValidateExpression(schema, *condition));
     GDV_RETURN_NOT_OK(PrecompileProjector(schema, staged.pre, SelectionMode::kNone));

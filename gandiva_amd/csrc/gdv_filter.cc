@@ -33,7 +33,7 @@ Status Filter::Make(const Schema& schema, const ExpressionPtr& condition,
   f->small_filter_.store(!EngineKnobs::Get().no_small_filter);
   ExpressionPtr planned = condition;
   StagedExpressions staged;
-  StageMaterialisedValues(schema, {condition}, &staged);
+  StageMaterialisedValues(schema, {condition}, &staged, opts);
   if (!staged.pre.empty()) {
     GDV_RETURN_NOT_OK(ValidateExpression(schema, *condition));
     GDV_RETURN_NOT_OK(Projector::Make(schema, staged.pre, SelectionMode::kNone, config, &f->pre_));

@@ -16,7 +16,7 @@ Status FilterProject::Make(const Schema& schema, const ExpressionPtr& condition,
   StagedExpressions staged;
   std::vector<ExpressionPtr> all = exprs;
   all.push_back(condition);
-  StageMaterialisedValues(schema, all, &staged);
+  StageMaterialisedValues(schema, all, &staged, CodegenOptions::FromEnv());
   if (!staged.pre.empty()) return Status::CodeGenError("fused filter-project: two-stage plans take the filter + projector chain");
   auto fp = std::make_shared<FilterProject>();
   fp->schema_ = schema;

@@ -4,10 +4,11 @@ namespace gdv {
 
 namespace {
 
-bool MaterialisesBytes(const Node& n) {
+bool MaterialisesBytes(const Node& n, bool utf8_case) {
   if (n.kind() != NodeKind::kFunction) return false;
   auto& fn = static_cast<const FunctionNode&>(n);
   const std::string& f = fn.name();
+  if (utf8_case && (f == "upper" || f == "lower")) return true;  // GDV_UTF8_CASE=1: values of their own kind
   if (f == "concat" || f == "concatOperator" || f == "lpad" || f == "rpad" || f == "reverse" || f == "replace" || f == "initcap" ||
       f == "hashSHA256" || f == "sha256" || f == "hashSHA1" || f == "sha1" || f == "sha" || f == "hashMD5" || f == "md5" ||
       f == "repeat" || f == "space" || f == "translate" || (planner::FnTraits(f) & planner::kFnEncode) != 0)
@@ -18,6 +19,7 @@ bool MaterialisesBytes(const Node& n) {
 struct Stager {
   const Schema& schema;
   StagedExpressions* out;
+  bool utf8_case;  // CodegenOptions::utf8_case of this Make
   std::map<std::string, NodePtr> field_of;  // hoisted sub-tree (cache key) -> its temporary field
 
   // `guard` (may be null): the condition under which the caller's tree evaluates `n` at all — the
@@ -62,7 +64,7 @@ struct Stager {
   }
   // `takes_bytes`: the parent is an output root or a concat — it can take a materialising child as it is
   NodePtr Rewrite(const NodePtr& n, bool takes_bytes, const NodePtr& guard) {
-    if (MaterialisesBytes(*n) && !takes_bytes) return Hoist(n, guard);  // (its own sub-tree is the first stage's business)
+    if (MaterialisesBytes(*n, utf8_case) && !takes_bytes) return Hoist(n, guard);  // (its own sub-tree is the first stage's business)
     switch (n->kind()) {
       case NodeKind::kFunction: {
         auto& fn = static_cast<const FunctionNode&>(*n);
@@ -119,11 +121,11 @@ struct Stager {
 }  // namespace
 
 void StageMaterialisedValues(const Schema& schema, const std::vector<ExpressionPtr>& exprs,
-                             StagedExpressions* out) {
+                             StagedExpressions* out, const CodegenOptions& opts) {
   out->pre.clear();
   out->main.clear();
   out->schema = schema;
-  Stager st{schema, out, {}};
+  Stager st{schema, out, opts.utf8_case, {}};
   for (auto& e : exprs) {
     if (!e || !e->root()) {
       out->main.push_back(e);

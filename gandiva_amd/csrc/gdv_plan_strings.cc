@@ -575,7 +575,8 @@ Status AssembleStrings(CodeGen& cg, KernelPlan* plan, const std::vector<std::str
     << "#define GDV_HIT_WORDS (GDV_SPAN_MAX / 64 + 4)\n"
     << "constexpr bool FULL = false;  // string tiles test `live` at run time (one code path)\n"
     << "#define GDV_OPTFLAT GDV_OPTFLAT_VALUE\n"
-    << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n"
+    << "#define GDV_STAGE_COPY(dst, v) " << cg.WrapCopy(cg.StageCopyFn("gdv_stage_copy") + "(dst, v)") << "\n"
+    << cg.StrCopyDefine()
     << AblDefine()
     << "#define GDV_OUT(e, v) if (live) "
     << (plan->opts.nontemporal ? "gdv_stnt" : "gdv_st") << "(out##e, row, (v))\n";
@@ -713,7 +714,7 @@ Status AssembleStrings(CodeGen& cg, KernelPlan* plan, const std::vector<std::str
     std::string text = tmpl;
     size_t p0 = text.find("GDV_OPTFLAT_VALUE");
     text.replace(p0, strlen("GDV_OPTFLAT_VALUE"), optflat);
-    FinishKernel(std::move(text), /*all_occurrences=*/false, name_out, src_out);
+    FinishKernel(std::move(text), /*all_occurrences=*/false, name_out, src_out, cg.utf8_case_ ? "uc" : "");
   };
   const std::string tmpl = s.str();
   finish(tmpl, plan->has_flat_output ? "1" : "0", &plan->kernel_name, &plan->source);
@@ -789,12 +790,13 @@ Status AssembleStringsWave(CodeGen& cg, KernelPlan* plan, const std::vector<std:
     const std::string M = std::to_string(mirror_slot);
     const std::string where = "mir" + M + ", sd" + M + " + sb" + M + ", hm_ok" + M + " ? se" + M + " - sb" + M + " : 0";
     if (cg.replace_hook_ >= 0)
-      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mirh") << "(dst, v, " << where << ", hit" << cg.replace_hook_ << ")\n";
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.WrapCopy(cg.StageCopyFn("gdv_stage_copy_mirh") + "(dst, v, " + where + ", hit" + std::to_string(cg.replace_hook_) + ")") << "\n";
     else
-      s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy_mir") << "(dst, v, " << where << ")\n";
+      s << "#define GDV_STAGE_COPY(dst, v) " << cg.WrapCopy(cg.StageCopyFn("gdv_stage_copy_mir") + "(dst, v, " + where + ")") << "\n";
   } else {
-    s << "#define GDV_STAGE_COPY(dst, v) " << cg.StageCopyFn("gdv_stage_copy") << "(dst, v)\n";
+    s << "#define GDV_STAGE_COPY(dst, v) " << cg.WrapCopy(cg.StageCopyFn("gdv_stage_copy") + "(dst, v)") << "\n";
   }
+  s << cg.StrCopyDefine();
 
   s << "GDV_DEV void gdv_tile(const gdv_args& A, const gdv_int64 wt, const int lane, const int wave,\n"
     << "                      gdv_uint8* lds_out, gdv_uint64* lds_hit, gdv_uint8* lds_in) {\n"
@@ -989,7 +991,7 @@ Status AssembleStringsWave(CodeGen& cg, KernelPlan* plan, const std::vector<std:
       << (mirror_slot >= 0 ? "gdv_lds_in[wave]" : "nullptr") << ");\n";
   s << "}\n";
 
-  FinishKernel(s.str(), /*all_occurrences=*/false, &plan->kernel_name, &plan->source);
+  FinishKernel(s.str(), /*all_occurrences=*/false, &plan->kernel_name, &plan->source, cg.utf8_case_ ? "uc" : "");
   plan->ir = plan->source;
   return Status::OK();
 }

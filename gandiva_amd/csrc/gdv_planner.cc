@@ -36,6 +36,7 @@ CodegenOptions CodegenOptions::FromEnv() {
   o.no_sel_wave = std::getenv("GDV_NO_SEL_WAVE") != nullptr;
   if (const char* s = std::getenv("GDV_PREPASS_AHEAD")) o.prepass_ahead = atoi(s) != 0;
   if (const char* s = std::getenv("GDV_CAST_X86_INDEFINITE")) o.cast_x86_indefinite = atoi(s) != 0;
+  if (const char* s = std::getenv("GDV_UTF8_CASE")) o.utf8_case = atoi(s) != 0;
   if (const char* s = std::getenv("GDV_SWEEP_GROUP")) o.sweep_group = std::max(1, std::min(8, atoi(s)));
   if (const char* s = std::getenv("GDV_FP_EXPERIMENT")) o.fp_experiment = atoi(s);
   if (const char* s = std::getenv("GDV_FP_K")) o.fp_rounds = std::max(1, std::min(8, atoi(s)));
@@ -48,7 +49,7 @@ std::string CodegenOptions::Key() const {
          (nt_loads ? "ntl" : "") + (lds_mirror ? "" : "nm") + (subtiles_forced ? "U" : "") + (waves_forced ? "W" : "") +
          (no_inline_string_args ? "ni" : "") + (no_wave_shape ? "nw" : "") + (wave_bytefree_only ? "bf" : "") +
          (ablation ? "abl" : "") + (runtime_needles ? "rn" : "") + (prepass_rolled ? "pr" : "") + (rows_word ? "rw" : "") + (no_sel_wave ? "nsw" : "") + (prepass_ahead ? "" : "npa") + (fp_experiment ? "fx" + std::to_string(fp_experiment) : "") + (fp_rounds != 3 ? "k" + std::to_string(fp_rounds) : "") +
-         (fp_window_bytes != 9984 ? "fw" + std::to_string(fp_window_bytes) : "") + (cast_x86_indefinite ? "xi" : "") + (sweep_group != 1 ? "sg" + std::to_string(sweep_group) : "");
+         (fp_window_bytes != 9984 ? "fw" + std::to_string(fp_window_bytes) : "") + (cast_x86_indefinite ? "xi" : "") + (sweep_group != 1 ? "sg" + std::to_string(sweep_group) : "") + (utf8_case ? "uc" : "");
 }
 
 namespace {
@@ -59,7 +60,7 @@ enum class StringShape { kScanner, kWaveMain, kWavePrepass, kWaveMainExact, kWav
 // every string is assumed ASCII?  (offsets, validity bitmaps, fixed-width values and literals are
 // free.)  Outputs with that property let a plan take the wave shape: their byte totals come from a
 // pre-pass over the offsets.
-bool ByteFree(const Node& n) {
+bool ByteFree(const Node& n, bool utf8_case) {
   static const std::set<std::string> over_strings = {
       "substr", "substring", "left", "right", "upper", "lower", "octet_length", "bit_length", "char_length",
       "length", "lengthUtf8", "castVARCHAR", "concat", "concatOperator", "reverse", "initcap", "lpad", "rpad", "isnull", "hashSHA256", "sha256",
@@ -74,22 +75,23 @@ bool ByteFree(const Node& n) {
       auto& fn = static_cast<const FunctionNode&>(n);
       bool takes_strings = false;
       for (auto& c : fn.children()) {
-        if (!ByteFree(*c)) return false;
+        if (!ByteFree(*c, utf8_case)) return false;
         takes_strings |= c->return_type().is_varlen();
       }
+      if (utf8_case && (fn.name() == "upper" || fn.name() == "lower")) return false;  // the length follows from the bytes
       return !takes_strings || over_strings.count(fn.name()) != 0;
     }
     case NodeKind::kIf: {
       auto& i = static_cast<const IfNode&>(n);
-      return ByteFree(*i.condition()) && ByteFree(*i.then_node()) && ByteFree(*i.else_node());
+      return ByteFree(*i.condition(), utf8_case) && ByteFree(*i.then_node(), utf8_case) && ByteFree(*i.else_node(), utf8_case);
     }
     case NodeKind::kBoolean:
       for (auto& c : static_cast<const BooleanNode&>(n).children())
-        if (!ByteFree(*c)) return false;
+        if (!ByteFree(*c, utf8_case)) return false;
       return true;
     case NodeKind::kIn: {
       auto& in = static_cast<const InNode&>(n);
-      return !in.value_type().is_varlen() && ByteFree(*in.eval());
+      return !in.value_type().is_varlen() && ByteFree(*in.eval(), utf8_case);
     }
   }
   return false;
@@ -439,7 +441,7 @@ Status PlanProjector(const Schema& schema, const std::vector<ExpressionPtr>& exp
   for (auto& e : exprs) {
     if (!e->result().type.is_varlen()) continue;
     any_varlen_out = true;
-    if (bytefree_only) wave_ok = wave_ok && ByteFree(*e->root());
+    if (bytefree_only) wave_ok = wave_ok && ByteFree(*e->root(), opts.utf8_case);
   }
   if (!(wave_ok && any_varlen_out))
     return PlanProjectorShape(schema, exprs, mode, opts, StringShape::kScanner, nullptr, plan, nullptr, compact_from);

@@ -62,6 +62,7 @@ struct CodegenOptions {
   // first pieces requested back to back (GDV_U loads in flight per lane; one bitmap per sub-tile in LDS).  GDV_PREPASS_AHEAD=0:
   // one span per row-loop iteration, the next one's first piece prefetched (round 4).
   bool prepass_ahead = true;
+  bool utf8_case = false;              // GDV_UTF8_CASE=1 at Make: upper / lower map every character through utf8proc's simple case map (default: ASCII letters only)
   bool no_sel_wave = false;            // GDV_NO_SEL_WAVE=1: selection-mode var-len plans take the scanner shape (rounds 2-4)
   bool runtime_needles = false;        // GDV_RUNTIME_NEEDLES=1: wave kernels load their '%needle%' bytes instead of carrying them as immediates
   static CodegenOptions FromEnv();
@@ -102,6 +103,7 @@ struct KernelPlan {
   std::vector<uint64_t> literals;  // fixed-width literal values -> gdv_args::lit (kernel arguments)
   std::string const_block;         // string literals, LIKE patterns, IN tables -> device memory (aux0)
   bool can_raise = false;          // kernel may set error bits
+  std::string utf8_case_fns;       // GDV_UTF8_CASE=1: "upper", "lower" or "upper / lower" when the plan maps through utf8proc's table (they raise on text that is not UTF-8)
   bool exprs_raise = false;        // fused filter-project: some EXPRESSION can raise (can_raise is always set there: the look-back's stall bit)
   // Some output is utf8/binary: single launch, workgroup 0 scans the tile totals (granules in
   // `mask`, grand totals in `counts`); workers are workgroups 1.. (gdv_planner.cc, string plans)
@@ -166,7 +168,8 @@ struct StagedExpressions {
   Schema schema;                    // caller's schema + one field per first-stage expression
   std::vector<ExpressionPtr> main;  // the caller's expressions, rewritten over `schema`
 };
+// (opts.utf8_case: upper / lower are such values too)
 void StageMaterialisedValues(const Schema& schema, const std::vector<ExpressionPtr>& exprs,
-                             StagedExpressions* out);
+                             StagedExpressions* out, const CodegenOptions& opts);
 
 }  // namespace gdv

@@ -92,6 +92,7 @@ class CodeGen {
   Status GenRegexpExtract(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenReplace(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenTranslate(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
+  Status GenUtf8Case(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenPad(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenConcat(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenToDate(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
@@ -193,7 +194,15 @@ class CodeGen {
   bool encode_ = false;            // a hex / unhex / base64 / unbase64 value is copied: ... the *_enc entry points
   // the output copy of a var-len value (the *_ext entry: translate values, *_dt: dates and times, *_enc: hex / base64 and
   // their inverses; only plans that hold one use it)
-  std::string CopyFn() const { return StageCopyFn("gdv_str_copy"); }
+  // (a plan that holds an upper / lower value of GDV_UTF8_CASE=1 wraps whichever entry it is: GDV_STR_COPY / GDV_STAGE_COPY
+  // are macros of the kernel's own text then, defined by the skeleton through WrapCopy)
+  bool utf8_case_ = false;
+  std::map<int, std::string> case_tables_;  // direction (1 upper, 2 lower) -> its table in the constant block
+  std::string CopyFn() const { return utf8_case_ ? "GDV_STR_COPY" : StageCopyFn("gdv_str_copy"); }
+  std::string WrapCopy(const std::string& call) const { return utf8_case_ ? "GDV_COPY_UTF8CASE(dst, v, " + call + ")" : call; }
+  std::string StrCopyDefine() const {
+    return utf8_case_ ? "#define GDV_STR_COPY(dst, v) " + WrapCopy(StageCopyFn("gdv_str_copy") + "(dst, v)") + "\n" : "";
+  }
   std::string StageCopyFn(const std::string& base) const {
     return base + (translate_ ? "_ext" : "") + (datetime_ ? "_dt" : "") + (encode_ ? "_enc" : "");
   }
@@ -244,7 +253,8 @@ struct Assembler {
 };
 // names the kernel after its text (and the library functions it reaches) and substitutes GDV_KERNEL_NAME: every occurrence,
 // or the first one only (string kernels have a single entry point)
-void FinishKernel(std::string text, bool all_occurrences, std::string* name, std::string* source);
+// `tag`: appended to the name (plans that hold a value of a Make-time option carry the option's Key() tag: "uc")
+void FinishKernel(std::string text, bool all_occurrences, std::string* name, std::string* source, const std::string& tag = std::string());
 std::string SelCType(SelectionMode m);
 void BindInputs(CodeGen& cg, KernelPlan* plan);  // what a plan records of its generation: the input slots, can_raise, the argument layout
 // selection mode, inside the load loop: the slot's row (srow[u]) and every input gathered through it

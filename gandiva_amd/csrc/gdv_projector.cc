@@ -11,6 +11,15 @@ LruCache<Projector>& ProjectorCache() {
   return c;
 }
 
+// an "invalid argument" of a plan whose upper / lower map through utf8proc's table names them: they are what raises on text
+// that is not UTF-8
+std::string RaiseMessage(const KernelPlan& plan, uint32_t bits) {
+  std::string m = ErrorMessage(bits);
+  if ((bits & 4u) && !plan.utf8_case_fns.empty())
+    m += " (" + plan.utf8_case_fns + " under GDV_UTF8_CASE=1: text that is not UTF-8 raises)";
+  return m;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ Projector
@@ -48,7 +57,7 @@ Status Projector::Make(const Schema& schema, const std::vector<ExpressionPtr>& e
   StagedExpressions staged;
   // (round 3: in every selection mode — the first stage is built in the SAME mode, so it evaluates,
   // and can raise, only on the selected rows, and writes one temporary row per slot)
-  StageMaterialisedValues(schema, exprs, &staged);
+  StageMaterialisedValues(schema, exprs, &staged, opts);
   if (!staged.pre.empty()) {
     for (auto& e : exprs) GDV_RETURN_NOT_OK(ValidateExpression(schema, *e));  // errors name the caller's trees
     GDV_RETURN_NOT_OK(Projector::Make(schema, staged.pre, mode, config, &p->pre_));
@@ -248,7 +257,7 @@ Status Projector::EvaluateVarlen(VarlenLaunch& vlaunch, ArgBlock& args, Staging&
                                  std::to_string(have) + " < " + std::to_string(totals[e]) +
                                  " bytes needed (data_size updated; retry with a larger buffer)");
   }
-  if (err_bits != 0) return Status::ExecutionError(ErrorMessage(err_bits));
+  if (err_bits != 0) return Status::ExecutionError(RaiseMessage(plan_, err_bits));
   GDV_RETURN_NOT_OK(capacity);
   if (mem == MemKind::kHost) {
     bool any = false;
@@ -390,7 +399,7 @@ Status Projector::Evaluate(int64_t num_rows, const ColumnBuffers* cols, int num_
   }
   const bool must_sync = mem == MemKind::kHost || (plan_.can_raise && err_word == nullptr) || !(flags & kEvalAsync) || two_stage;
   if (must_sync) GDV_HIP_RETURN_NOT_OK(hipStreamSynchronize(stream));
-  if (err_bits != 0) return Status::ExecutionError(ErrorMessage(err_bits));
+  if (err_bits != 0) return Status::ExecutionError(RaiseMessage(plan_, err_bits));
   if (mem == MemKind::kHost) st.Deliver();
   return Status::OK();
 }
@@ -465,7 +474,7 @@ Status Projector::EvaluateMany(const BatchView* batches, int nb, hipStream_t str
   }
   GDV_HIP_RETURN_NOT_OK(hipStreamSynchronize(stream));
   drain.armed = false;
-  if (err_bits != 0) return Status::ExecutionError(ErrorMessage(err_bits));
+  if (err_bits != 0) return Status::ExecutionError(RaiseMessage(plan_, err_bits));
   return Status::OK();
 }
 

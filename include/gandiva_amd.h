@@ -216,6 +216,17 @@ gdv_type_t gdv_expression_result_type(const gdv_expression_t* expr);
 void gdv_expression_free(gdv_expression_t* expr);
 
 /* ---- Projector -------------------------------------------------------------------- */
+/* Environment, read at every Make (projector, filter, filter-project) and never during Evaluate; each is part of the cache
+ * key, so objects made with and without it coexist in one process:
+ *   GDV_CAST_X86_INDEFINITE=1  float -> integer casts of NaN / out-of-range values give the x86 "indefinite integer"
+ *                              (0x80..0) instead of saturating (PARITY.md, numeric casts).
+ *   GDV_UTF8_CASE=1            upper(utf8) / lower(utf8) map every character through utf8proc's simple case map instead of
+ *                              ASCII letters only (PARITY.md, `upper lower`).  The result's length then follows from the bytes:
+ *                              a row that is not UTF-8 (a byte that cannot lead a character, a character cut by the end of the
+ *                              text, a continuation byte that is not 10xxxxxx) makes Evaluate fail with an ExecutionError
+ *                              ("invalid argument", naming upper / lower); a null row never does.  Sequences that are
+ *                              well-formed but not Unicode (over-long forms, surrogates, above U+10FFFF) are copied.  initcap,
+ *                              ilike and the regular expressions are not affected. */
 int gdv_projector_make(const gdv_schema_t* schema, gdv_expression_t* const* exprs, int num_exprs,
                        int selection_mode, const gdv_config_t* config /* NULL = default */,
                        gdv_projector_t** out);
