@@ -230,6 +230,7 @@ Status CodeGen::Gen(const Node& node, const std::string& active, Val* out) {
       if (name == "replace") return GenReplace(fn, args, active, out);
       if (name == "translate") return GenTranslate(fn, args, active, out);
       if (utf8_case) return GenUtf8Case(fn, args, active, out);
+      if (name.compare(0, 4, "mask") == 0) return GenMask(fn, args, active, out);
       if (name == "lpad" || name == "rpad") return GenPad(fn, args, active, out);
       if (is_concat) return GenConcat(fn, args, active, out);
       if (def->flags & kDateFormatArg) return GenToDate(fn, args, active, out);

@@ -20,6 +20,8 @@ unsigned FnTraits(const std::string& name) {
   static const std::map<std::string, unsigned> k = {
       {"reverse", kFnOpaque | kFnAsciiHint}, {"replace", kFnOpaque}, {"initcap", kFnOpaque}, {"repeat", kFnOpaque},
       {"space", kFnOpaque}, {"translate", kFnOpaque},
+      {"mask", kFnOpaque}, {"mask_first_n", kFnOpaque}, {"mask_last_n", kFnOpaque}, {"mask_show_first_n", kFnOpaque},
+      {"mask_show_last_n", kFnOpaque},
       {"sha256", kFnDigest}, {"sha1", kFnDigest}, {"sha", kFnDigest}, {"md5", kFnDigest},
       {"hex", kFnEncode}, {"to_hex", kFnEncode}, {"unhex", kFnEncode}, {"from_hex", kFnEncode}, {"base64", kFnEncode}, {"unbase64", kFnEncode},
       {"substr", kFnAsciiHint}, {"substring", kFnAsciiHint}, {"left", kFnAsciiHint}, {"right", kFnAsciiHint},
@@ -289,6 +291,45 @@ Status CodeGen::GenUtf8Case(const FunctionNode& fn, FnArgs& args, const std::str
   utf8_case_ = true;
   const std::string guard = AndExpr(AndExpr("live", active), LaneValid(*out));
   out->v = Tmp("gdv_str", guard + " ? gdv_utf8_case(ctx, " + args[0].v + ", " + it->second + ") : gdv_empty_str()");
+  return Status::OK();
+}
+
+Status CodeGen::GenMask(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out) {
+  // mask(text[, upper[, lower[, digit]]]) with LITERAL one-byte replacements below 0x80 (defaults 'X', 'x', 'n') and
+  // mask_first_n / mask_last_n / mask_show_first_n / mask_show_last_n(text, n) with a literal or per-row n: the row packs the
+  // parameters into the value and reads no byte, the output copy classifies and writes (gdv_device_lib.hpp, GDV_MAP_MASK)
+  (void)active;
+  const std::string& name = fn.name();
+  int mode = 0;  // GDV_MASK_ALL ...
+  unsigned reps = 'X' | ('x' << 8) | ('n' << 16);
+  std::string n = "0";
+  if (name == "mask") {
+    bool null_literal = false;
+    for (size_t i = 1; i < args.size(); i++) {
+      const Node& c = *fn.children()[i];
+      const bool literal = c.kind() == NodeKind::kLiteral;
+      const std::string* bytes = literal ? &static_cast<const LiteralNode&>(c).value().bytes : nullptr;
+      if (literal && static_cast<const LiteralNode&>(c).is_null()) {
+        null_literal = true;
+        continue;
+      }
+      if (!literal || bytes->size() != 1 || static_cast<unsigned char>((*bytes)[0]) >= 0x80)
+        return Status::CodeGenError("Function " + fn.ToString() + " not supported yet: the HIP backend takes mask with "
+                                    "literal replacement characters of exactly one byte below 0x80 only (argument " +
+                                    std::to_string(i + 1) + " is " + (!literal ? "not a literal" : bytes->empty() ? "empty" :
+                                    bytes->size() > 1 ? "longer than one byte" : "a byte >= 0x80") + "). ");
+      reps = (reps & ~(0xFFu << (8 * (i - 1)))) | (static_cast<unsigned>(static_cast<unsigned char>((*bytes)[0])) << (8 * (i - 1)));
+    }
+    out->vcols = args[0].vcols;
+    if (null_literal) return NullString(out);
+    out->vlane = args[0].vlane;
+  } else {
+    mode = name == "mask_first_n" ? 1 : name == "mask_last_n" ? 2 : name == "mask_show_first_n" ? 3 : 4;
+    n = args[1].v;
+    out->vlane = MergeArgValidity(args, out);
+  }
+  mask_ = true;
+  out->v = Tmp("gdv_str", "gdv_mask(" + args[0].v + ", " + std::to_string(mode) + ", (gdv_int32)(" + n + "), " + std::to_string(reps) + "u)");
   return Status::OK();
 }
 

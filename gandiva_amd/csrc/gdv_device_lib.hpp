@@ -3664,6 +3664,121 @@ GDV_DEV void gdv_copy_utf8_case(P dst, const gdv_str& s) {
   }
 }
 
+// ------------------------------------------------------------------ data masking: mask, mask_first_n, mask_last_n,
+// mask_show_first_n, mask_show_last_n.  A masked byte 'A'..'Z' becomes the upper replacement, 'a'..'z' the lower one, '0'..'9'
+// the digit one (literals of one byte < 0x80: the planner checks them); every other byte, every byte >= 0x80 included, is
+// copied, so the result has the text's length.  n counts characters; a character starts at every byte that is not 10xxxxxx
+// (nothing is validated, nothing raises).  With c characters and k = min(max(n, 0), c): first_n masks characters [0, k),
+// last_n [c - k, c), show_first_n [k, c), show_last_n [0, c - k).  [recollection + decisions: PARITY.md, `mask`]
+// A value of its own kind, GDV_MAP_MASK, as translate's is: the row function reads no byte — it keeps p / len / the ASCII case
+// map / GDV_STR_INBUF and packs into `lead` n (bits 0..31), the upper / lower / digit replacement (bits 32..55) and the mode
+// (bits 56..58); lead_p is unused.  The copy does the work: the masked characters are one byte range [b0, b1) of the row, found
+// from the lead bytes of its words (popcount of the "not 10xxxxxx" bits; the last_n pair walks back from the row's end), then
+// every word is classified with the carry-free range tests of gdv_map8 and the replacement bytes are selected under a per-byte
+// mask.  Views readable with raw 8-byte loads (GDV_STR_INBUF) go eight bytes per step; a byte loop serves the others.
+// Plans that hold such a value copy through GDV_COPY_MASK around the entry point they would use without it.
+#define GDV_MAP_MASK 2097152
+#define GDV_COPY_MASK(dst, v, otherwise) \
+  do { if ((v).map & GDV_MAP_MASK) gdv_copy_masked(dst, v); else otherwise; } while (0)
+#define GDV_MASK_ALL 0
+#define GDV_MASK_FIRST_N 1
+#define GDV_MASK_LAST_N 2
+#define GDV_MASK_SHOW_FIRST_N 3
+#define GDV_MASK_SHOW_LAST_N 4
+// reps: upper | lower << 8 | digit << 16
+GDV_DEV gdv_str gdv_mask(gdv_str s, gdv_int32 mode, gdv_int32 n, gdv_uint32 reps) {
+  s.lead = (gdv_uint64)(gdv_uint32)n | ((gdv_uint64)(reps & 0xFFFFFFu) << 32) | ((gdv_uint64)mode << 56);
+  s.lead_p = nullptr;
+  s.flags &= GDV_STR_INBUF;
+  s.map = (s.map & GDV_MAP_CASE) | GDV_MAP_MASK;
+  return s;
+}
+// bit 7 of every byte of w that starts a character (is not 10xxxxxx)
+GDV_DEV gdv_uint64 gdv_lead_bits8(gdv_uint64 w) { return ~(w & ~(w << 1)) & GDV_B80; }
+// byte offset of the character with 0-based index k >= 0 of the `len` bytes at p, `len` when there are fewer
+GDV_DEV gdv_int32 gdv_mask_pos_fwd(const gdv_uint8* p, gdv_int32 len, bool words, gdv_int32 k) {
+  if (words) {
+    for (gdv_int32 i = 0; i < len; i += 8) {
+      gdv_uint64 lead = gdv_lead_bits8(gdv_load8_raw(p + i)) & gdv_low_bytes_mask(len - i);
+      const gdv_int32 c = (gdv_int32)__popcll(lead);
+      if (k < c) {
+        for (; k > 0; k--) lead &= lead - 1;  // drop the characters before it
+        return i + (gdv_int32)(__builtin_ctzll(lead) >> 3);
+      }
+      k -= c;
+    }
+    return len;
+  }
+  for (gdv_int32 i = 0; i < len; i++)
+    if ((p[i] & 0xC0) != 0x80 && k-- == 0) return i;
+  return len;
+}
+// byte offset of the k-th character from the end (k >= 1), 0 when there are fewer
+GDV_DEV gdv_int32 gdv_mask_pos_back(const gdv_uint8* p, gdv_int32 len, bool words, gdv_int32 k) {
+  if (words) {
+    for (gdv_int32 e = len; e > 0;) {
+      const gdv_int32 b = e > 8 ? e - 8 : 0;  // (the load starts inside the view)
+      gdv_uint64 lead = gdv_lead_bits8(gdv_load8_raw(p + b)) & gdv_low_bytes_mask(e - b);
+      const gdv_int32 c = (gdv_int32)__popcll(lead);
+      if (k <= c) {
+        for (; k > 1; k--) lead &= ~(1ull << (63 - __builtin_clzll(lead)));  // drop the characters behind it
+        return b + (gdv_int32)((63 - __builtin_clzll(lead)) >> 3);
+      }
+      k -= c;
+      e = b;
+    }
+    return 0;
+  }
+  for (gdv_int32 i = len - 1; i >= 0; i--)
+    if ((p[i] & 0xC0) != 0x80 && --k == 0) return i;
+  return 0;
+}
+// the 0xFF bytes of the ASCII bytes of w in ['A','Z'] (*up), ['a','z'] (*lo), ['0','9'] (*dg): gdv_map8's range test, the top
+// bit of each byte widened to the byte (no carry crosses a byte: 0x01 * 0xFF)
+GDV_DEV void gdv_mask_classes8(gdv_uint64 w, gdv_uint64* up, gdv_uint64* lo, gdv_uint64* dg) {
+  const gdv_uint64 h = w & GDV_B7F, ascii = ~w & GDV_B80;
+  *up = (((h + 0x3f3f3f3f3f3f3f3full) & ~(h + 0x2525252525252525ull) & ascii) >> 7) * 0xFFull;  // 0x80 - 'A' | 0x7f - 'Z'
+  *lo = (((h + 0x1f1f1f1f1f1f1f1full) & ~(h + 0x0505050505050505ull) & ascii) >> 7) * 0xFFull;  // 0x80 - 'a' | 0x7f - 'z'
+  *dg = (((h + 0x5050505050505050ull) & ~(h + 0x4646464646464646ull) & ascii) >> 7) * 0xFFull;  // 0x80 - '0' | 0x7f - '9'
+}
+// (writes exactly the bytes [0, s.len) of dst)
+template <typename P>
+GDV_DEV void gdv_copy_masked(P dst, const gdv_str& s) {
+  const gdv_int32 len = s.len, cm = s.map & GDV_MAP_CASE;
+  if (len <= 0) return;
+  const bool words = (s.flags & GDV_STR_INBUF) != 0;
+  const gdv_int32 mode = (gdv_int32)((s.lead >> 56) & 7), n = (gdv_int32)(gdv_uint32)s.lead;
+  const gdv_uint8 ru = (gdv_uint8)(s.lead >> 32), rl = (gdv_uint8)(s.lead >> 40), rd = (gdv_uint8)(s.lead >> 48);
+  // the masked bytes [b0, b1): bytes >= 0x80 inside are copied anyway, so only whole characters' ASCII bytes matter
+  gdv_int32 b0 = 0, b1 = len;
+  if (mode == GDV_MASK_FIRST_N) b1 = n <= 0 ? 0 : gdv_mask_pos_fwd(s.p, len, words, n);
+  else if (mode == GDV_MASK_SHOW_FIRST_N) b0 = n <= 0 ? 0 : gdv_mask_pos_fwd(s.p, len, words, n);
+  else if (mode == GDV_MASK_LAST_N) b0 = n <= 0 ? len : gdv_mask_pos_back(s.p, len, words, n);
+  else if (mode == GDV_MASK_SHOW_LAST_N) b1 = n <= 0 ? len : gdv_mask_pos_back(s.p, len, words, n);
+  if (words) {
+    const gdv_uint64 wu = ru * 0x0101010101010101ull, wl = rl * 0x0101010101010101ull, wd = rd * 0x0101010101010101ull;
+    for (gdv_int32 i = 0; i < len; i += 8) {
+      const gdv_int32 r = len - i < 8 ? len - i : 8;
+      gdv_uint64 w = gdv_map8(gdv_load8_raw(s.p + i), cm);
+      const gdv_int32 from = b0 - i < 0 ? 0 : (b0 - i > 8 ? 8 : b0 - i), to = b1 - i < 0 ? 0 : (b1 - i > 8 ? 8 : b1 - i);
+      const gdv_uint64 in = gdv_low_bytes_mask(to) & ~gdv_low_bytes_mask(from);  // bytes of this word inside [b0, b1)
+      gdv_uint64 up, lo, dg;
+      gdv_mask_classes8(w, &up, &lo, &dg);
+      up &= in;
+      lo &= in;
+      dg &= in;
+      w = (w & ~(up | lo | dg)) | (wu & up) | (wl & lo) | (wd & dg);
+      if (r == 8) __builtin_memcpy(dst + i, &w, 8); else gdv_store_low_bytes(dst + i, w, r);
+    }
+    return;
+  }
+  for (gdv_int32 i = 0; i < len; i++) {
+    gdv_uint8 c = gdv_map_byte(s.p[i], cm);
+    if (i >= b0 && i < b1) c = (c >= 'A' && c <= 'Z') ? ru : (c >= 'a' && c <= 'z') ? rl : (c >= '0' && c <= '9') ? rd : c;
+    dst[i] = c;
+  }
+}
+
 // ------------------------------------------------------------------ text <-> date / time: castDATE, castTIMESTAMP, castTIME
 // of text; castVARCHAR of date32, date64, timestamp, time32; castTIME(timestamp), castTIMESTAMP(date32).  Timestamps and times
 // are milliseconds.  Every function is null if null; a row that does not parse raises GDV_ERR_BAD_ARG.

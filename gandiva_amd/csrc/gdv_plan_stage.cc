@@ -11,7 +11,8 @@ bool MaterialisesBytes(const Node& n, bool utf8_case) {
   if (utf8_case && (f == "upper" || f == "lower")) return true;  // GDV_UTF8_CASE=1: values of their own kind
   if (f == "concat" || f == "concatOperator" || f == "lpad" || f == "rpad" || f == "reverse" || f == "replace" || f == "initcap" ||
       f == "hashSHA256" || f == "sha256" || f == "hashSHA1" || f == "sha1" || f == "sha" || f == "hashMD5" || f == "md5" ||
-      f == "repeat" || f == "space" || f == "translate" || (planner::FnTraits(f) & planner::kFnEncode) != 0)
+      f == "repeat" || f == "space" || f == "translate" || f == "mask" || f == "mask_first_n" || f == "mask_last_n" ||
+      f == "mask_show_first_n" || f == "mask_show_last_n" || (planner::FnTraits(f) & planner::kFnEncode) != 0)
     return true;
   return f == "castVARCHAR" && !fn.children().empty() && !fn.children()[0]->return_type().is_varlen();
 }

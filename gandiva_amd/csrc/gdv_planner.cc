@@ -65,6 +65,7 @@ bool ByteFree(const Node& n, bool utf8_case) {
       "substr", "substring", "left", "right", "upper", "lower", "octet_length", "bit_length", "char_length",
       "length", "lengthUtf8", "castVARCHAR", "concat", "concatOperator", "reverse", "initcap", "lpad", "rpad", "isnull", "hashSHA256", "sha256",
       "hashSHA1", "sha1", "sha", "hashMD5", "md5", "repeat",
+      "mask", "mask_first_n", "mask_last_n", "mask_show_first_n", "mask_show_last_n",  // (the length is the text's)
       "hex", "to_hex", "unhex", "from_hex", "base64",  // (unbase64 reads the row's last word for the padding)
       "isnotnull"};
   switch (n.kind()) {

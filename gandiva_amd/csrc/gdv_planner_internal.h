@@ -93,6 +93,7 @@ class CodeGen {
   Status GenReplace(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenTranslate(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenUtf8Case(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
+  Status GenMask(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenPad(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenConcat(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
   Status GenToDate(const FunctionNode& fn, FnArgs& args, const std::string& active, Val* out);
@@ -198,10 +199,15 @@ class CodeGen {
   // are macros of the kernel's own text then, defined by the skeleton through WrapCopy)
   bool utf8_case_ = false;
   std::map<int, std::string> case_tables_;  // direction (1 upper, 2 lower) -> its table in the constant block
-  std::string CopyFn() const { return utf8_case_ ? "GDV_STR_COPY" : StageCopyFn("gdv_str_copy"); }
-  std::string WrapCopy(const std::string& call) const { return utf8_case_ ? "GDV_COPY_UTF8CASE(dst, v, " + call + ")" : call; }
+  // (a plan that holds a mask / mask_*_n value wraps the entry the same way, with GDV_COPY_MASK; a plan that holds both nests them)
+  bool mask_ = false;
+  std::string CopyFn() const { return utf8_case_ || mask_ ? "GDV_STR_COPY" : StageCopyFn("gdv_str_copy"); }
+  std::string WrapCopy(const std::string& call) const {
+    const std::string inner = utf8_case_ ? "GDV_COPY_UTF8CASE(dst, v, " + call + ")" : call;
+    return mask_ ? "GDV_COPY_MASK(dst, v, " + inner + ")" : inner;
+  }
   std::string StrCopyDefine() const {
-    return utf8_case_ ? "#define GDV_STR_COPY(dst, v) " + WrapCopy(StageCopyFn("gdv_str_copy") + "(dst, v)") + "\n" : "";
+    return utf8_case_ || mask_ ? "#define GDV_STR_COPY(dst, v) " + WrapCopy(StageCopyFn("gdv_str_copy") + "(dst, v)") + "\n" : "";
   }
   std::string StageCopyFn(const std::string& base) const {
     return base + (translate_ ? "_ext" : "") + (datetime_ ? "_dt" : "") + (encode_ ? "_enc" : "");

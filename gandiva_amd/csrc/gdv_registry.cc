@@ -382,6 +382,13 @@ FunctionRegistry::FunctionRegistry() {
   add("space", {int64()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext);
   add("translate", {utf8(), utf8(), utf8()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult | kNeedsContext,
       "gdv_translate");  // planned by gdv_codegen_functions.cc, GenTranslate
+  // data masking: ASCII upper / lower / digit bytes become 'X' / 'x' / 'n' (or mask's literal one-byte replacements), every
+  // other byte is copied, so the length is the text's and nothing raises (no context); n counts characters.  Values the output
+  // copy materialises (GDV_MAP_MASK); planned by GenMask.  [recalled names, decided rules: PARITY.md, `mask`]
+  for (int nargs = 1; nargs <= 4; nargs++)
+    add("mask", std::vector<DataType>(nargs, utf8()), utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_mask");
+  for (const char* f : {"mask_first_n", "mask_last_n", "mask_show_first_n", "mask_show_last_n"})
+    add(f, {utf8(), int32()}, utf8(), NullPolicy::kNullIfNull, kVarlenResult, "gdv_mask");
   // bytes <-> printable text and checksums: hex / to_hex, unhex / from_hex, base64, unbase64 are values the output copy
   // materialises (GDV_MAP_ENCODE; the decoders raise on text they do not take), crc32 is the zlib CRC-32 widened to int64.
   // [RFC 4648 / zlib pin the bytes; letter case, raising and the widening are recalled: PARITY.md, hex / base64 / crc32]
