@@ -534,7 +534,11 @@ GDV_DEV gdv_int64 gdv_floor_div(gdv_int64 a, gdv_int64 b) {
   gdv_int64 q = a / b;
   return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
 }
-GDV_DEV gdv_int64 gdv_floor_mod(gdv_int64 a, gdv_int64 b) { return a - gdv_floor_div(a, b) * b; }
+// (from the remainder, not as a - floor_div * b: that product leaves int64 within the first partial day above INT64_MIN)
+GDV_DEV gdv_int64 gdv_floor_mod(gdv_int64 a, gdv_int64 b) {
+  const gdv_int64 r = a % b;
+  return (r != 0 && ((r < 0) != (b < 0))) ? r + b : r;
+}
 
 struct gdv_ymd {
   gdv_int64 y;
@@ -668,7 +672,7 @@ GDV_DEV gdv_int64 extractSecond_time32(gdv_time32 v) { return ((gdv_int64)v / 10
 // Month arithmetic clamps the day to the last day of the target month.
 GDV_DEV gdv_int64 gdv_add_months_ms(gdv_int64 millis, gdv_int64 months) {
   gdv_int64 days = gdv_floor_div(millis, GDV_MILLIS_IN_DAY);
-  gdv_int64 tod = millis - days * GDV_MILLIS_IN_DAY;
+  gdv_int64 tod = gdv_floor_mod(millis, GDV_MILLIS_IN_DAY);
   gdv_ymd c = gdv_civil_from_days(days);
   gdv_int64 total = c.y * 12 + (c.m - 1) + months;
   gdv_int64 ny = gdv_floor_div(total, 12);
@@ -731,27 +735,29 @@ GDV_TSDIFF(timestamp)
 // counted on (start, end) swapped into ascending order and negated afterwards.  The last month
 // counts when the end's day of month has reached the start's — or the end IS the last day of its
 // month (Jan 31 -> Feb 28 is one month) — and, on the same day of month, when the end's time of
-// day (whole seconds) has reached the start's.
-GDV_DEV gdv_int32 gdv_months_between(gdv_int64 s, gdv_int64 e) {
+// day (whole seconds) has reached the start's.  The count is exact in 64 bits (instants 2^31 months apart are about
+// 179 million years apart, and int64 milliseconds reach +-292 million): Quarter and Year divide the exact count and
+// only then narrow to the int32 the signature returns, so a result that fits is right even where the months do not.
+GDV_DEV gdv_int64 gdv_months_between(gdv_int64 s, gdv_int64 e) {
   const bool fwd = e > s;
   if (!fwd) { const gdv_int64 t = s; s = e; e = t; }
   const gdv_int64 sday = gdv_floor_div(s, GDV_MILLIS_IN_DAY), eday = gdv_floor_div(e, GDV_MILLIS_IN_DAY);
   const gdv_ymd a = gdv_civil_from_days(sday), b = gdv_civil_from_days(eday);
-  gdv_int32 m = (gdv_int32)(12 * (b.y - a.y) + (b.m - a.m));
+  gdv_int64 m = 12 * (b.y - a.y) + (b.m - a.m);
   if (b.d < a.d) {
     m -= b.d == gdv_last_day_of_month(b.y, b.m) ? 0 : 1;
   } else if (b.d == a.d) {
-    m -= (e - eday * GDV_MILLIS_IN_DAY) / 1000 >= (s - sday * GDV_MILLIS_IN_DAY) / 1000 ? 0 : 1;
+    m -= gdv_floor_mod(e, GDV_MILLIS_IN_DAY) / 1000 >= gdv_floor_mod(s, GDV_MILLIS_IN_DAY) / 1000 ? 0 : 1;
   }
   return fwd ? m : -m;
 }
 #define GDV_TSDIFF_MONTHS(T)                                                                      \
-  GDV_DEV gdv_int32 timestampdiffMonth_##T##_##T(gdv_##T s, gdv_##T e) { return gdv_months_between(s, e); } \
+  GDV_DEV gdv_int32 timestampdiffMonth_##T##_##T(gdv_##T s, gdv_##T e) { return (gdv_int32)gdv_months_between(s, e); } \
   GDV_DEV gdv_int32 timestampdiffQuarter_##T##_##T(gdv_##T s, gdv_##T e) {                        \
-    return gdv_months_between(s, e) / 3;                                                          \
+    return (gdv_int32)(gdv_months_between(s, e) / 3);                                             \
   }                                                                                               \
   GDV_DEV gdv_int32 timestampdiffYear_##T##_##T(gdv_##T s, gdv_##T e) {                           \
-    return gdv_months_between(s, e) / 12;                                                         \
+    return (gdv_int32)(gdv_months_between(s, e) / 12);                                            \
   }
 GDV_TSDIFF_MONTHS(date64)
 GDV_TSDIFF_MONTHS(timestamp)

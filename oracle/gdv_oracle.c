@@ -388,7 +388,10 @@ static int64_t floor_div(int64_t a, int64_t b) {
   int64_t q = a / b;
   return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
 }
-static int64_t floor_mod(int64_t a, int64_t b) { return a - floor_div(a, b) * b; }
+static int64_t floor_mod(int64_t a, int64_t b) {   /* (not a - floor_div * b: that product can leave int64) */
+  int64_t r = a % b;
+  return (r != 0 && ((r < 0) != (b < 0))) ? r + b : r;
+}
 static void civil_from_days(int64_t z, int64_t* y, int* m, int* d) {
   z += 719468;
   int64_t era = (z >= 0 ? z : z - 146096) / 146097;
@@ -415,7 +418,7 @@ static int last_dom(int64_t y, int m) {
   return (m == 2 && leap) ? 29 : t[m - 1];
 }
 static int64_t add_months(int64_t ms, int64_t months) {
-  int64_t days = floor_div(ms, MS_DAY), tod = ms - days * MS_DAY, y;
+  int64_t days = floor_div(ms, MS_DAY), tod = floor_mod(ms, MS_DAY), y;
   int m, d;
   civil_from_days(days, &y, &m, &d);
   int64_t total = y * 12 + (m - 1) + months;
@@ -1724,6 +1727,8 @@ static void eval_function(const node* n, ctx* c, int64_t row0, int cnt, const ui
       } else if (rt == T_DATE64 && t0 == T_DATE32) out->v[i].i = a[0].v[i].i * MS_DAY;
       else if (rt == T_DATE32 && t0 == T_DATE64) out->v[i].i = floor_div(a[0].v[i].i, MS_DAY);
       else if (rt == T_DATE64 && t0 == T_TS) out->v[i].i = floor_div(a[0].v[i].i, MS_DAY) * MS_DAY;
+      else if (rt == T_TS && t0 == T_DATE32) out->v[i].i = a[0].v[i].i * MS_DAY;
+      else if (rt == T_TIME32 && t0 == T_TS) out->v[i].i = floor_mod(a[0].v[i].i, MS_DAY);
       else out->v[i].i = wrap_int(rt, a[0].v[i].u);
     }
   } else if (!strcmp(f, "cbrt") || !strcmp(f, "exp") || !strcmp(f, "log10") || !strcmp(f, "sqrt") ||
@@ -1849,7 +1854,7 @@ static void eval_function(const node* n, ctx* c, int64_t row0, int cnt, const ui
       int64_t months = 12 * (ey - sy) + (em_ - sm_);
       if (edd < sdd) { if (edd != last_dom(ey, em_)) months--; }
       else if (edd == sdd) {
-        int64_t es = (e0 - ed * MS_DAY) / 1000, ss = (s0 - sd * MS_DAY) / 1000;
+        int64_t es = floor_mod(e0, MS_DAY) / 1000, ss = floor_mod(s0, MS_DAY) / 1000;
         if (es < ss) months--;
       }
       int64_t r = months / per;

@@ -63,6 +63,18 @@ def assert_bit_exact(got, want, what=""):
                              f"{gb[bad[:4]]} vs {wb[bad[:4]]}")
 
 
+def assert_bit_exact_where(got, want, keep, what=""):
+    """assert_bit_exact on the rows of the bool numpy array `keep`; on every other row only the validity is compared (a
+    row whose expected value is not defined, such as one whose exact result leaves int64, is still NULL or not NULL)."""
+    assert len(got) == len(want) == len(keep), f"{what}: lengths {len(got)}, {len(want)}, {len(keep)}"
+    gv, wv = validity_np(got), validity_np(want)
+    if not np.array_equal(gv, wv):
+        bad = np.flatnonzero(gv != wv)
+        raise AssertionError(f"{what}: validity differs at {len(bad)} rows, first {bad[:8]}")
+    mask = pa.array(np.asarray(keep, dtype=bool))
+    assert_bit_exact(got.filter(mask), want.filter(mask), what)
+
+
 def ulp_distance(g, w):
     """max distance in units of last place between two float64 numpy arrays."""
     both_nan = np.isnan(g) & np.isnan(w)

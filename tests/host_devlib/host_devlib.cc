@@ -689,4 +689,119 @@ void host_hash_numeric(int tk, int wide, const void* xv, void* outv, long n) {
   }
 }
 
+// ---------------------------------------------------------------- date and time on full-range operands
+// (tests/test_full_range_temporal_cpu.py).  tk: 0 date32, 1 date64, 2 timestamp.  The caller passes no row whose exact
+// result or intermediate leaves int64: signed overflow is undefined in these functions.
+#define HOST_EACH_TEMPORAL(X) X(0, date32) X(1, date64) X(2, timestamp)
+#define HOST_EACH_MILLIS(X) X(1, date64) X(2, timestamp)
+// op: 0 Year 1 Month 2 Day 3 Quarter 4 Doy 5 Dow 6 Hour 7 Minute 8 Second 9 Epoch 10 Decade 11 Century 12 Millennium
+void host_temporal_unary(int tk, int op, const void* xv, long long* out, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                                       \
+  case K: {                                                                                                           \
+    const gdv_##T v = ((const gdv_##T*)xv)[i];                                                                        \
+    out[i] = op == 0 ? extractYear_##T(v) : op == 1 ? extractMonth_##T(v) : op == 2 ? extractDay_##T(v)               \
+           : op == 3 ? extractQuarter_##T(v) : op == 4 ? extractDoy_##T(v) : op == 5 ? extractDow_##T(v)              \
+           : op == 6 ? extractHour_##T(v) : op == 7 ? extractMinute_##T(v) : op == 8 ? extractSecond_##T(v)           \
+           : op == 9 ? extractEpoch_##T(v) : op == 10 ? extractDecade_##T(v) : op == 11 ? extractCentury_##T(v)       \
+                     : extractMillennium_##T(v);                                                                      \
+    break;                                                                                                            \
+  }
+      HOST_EACH_TEMPORAL(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// op: 0..10 date_trunc_{Second, Minute, Hour, Day, Week, Month, Quarter, Year, Decade, Century, Millennium}, 11 extractWeek, 12 last_day
+void host_temporal_trunc(int tk, int op, const long long* x, long long* out, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+#define X(K, T)                                                                                                       \
+  case K: {                                                                                                           \
+    const gdv_##T v = x[i];                                                                                           \
+    out[i] = op == 0 ? date_trunc_Second_##T(v) : op == 1 ? date_trunc_Minute_##T(v) : op == 2 ? date_trunc_Hour_##T(v) \
+           : op == 3 ? date_trunc_Day_##T(v) : op == 4 ? date_trunc_Week_##T(v) : op == 5 ? date_trunc_Month_##T(v)   \
+           : op == 6 ? date_trunc_Quarter_##T(v) : op == 7 ? date_trunc_Year_##T(v) : op == 8 ? date_trunc_Decade_##T(v) \
+           : op == 9 ? date_trunc_Century_##T(v) : op == 10 ? date_trunc_Millennium_##T(v)                            \
+           : op == 11 ? extractWeek_##T(v) : last_day_##T(v);                                                         \
+    break;                                                                                                            \
+  }
+      HOST_EACH_MILLIS(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// op: 0..7 timestampadd{Second, Minute, Hour, Day, Week, Month, Quarter, Year}(count, v), 8 date_add(v, int64), 9 date_sub(v, int64),
+//     10 date_add(v, int32), 11 date_sub(v, int32); counts are int64 but for 10 and 11 (int32)
+void host_temporal_add(int tk, int op, const void* cv, const long long* x, long long* out, long n) {
+  for (long i = 0; i < n; i++) {
+    const gdv_int64 c = op >= 10 ? (gdv_int64)((const gdv_int32*)cv)[i] : ((const gdv_int64*)cv)[i];
+    switch (tk) {
+#define X(K, T)                                                                                                       \
+  case K: {                                                                                                           \
+    const gdv_##T v = x[i];                                                                                           \
+    out[i] = op == 0 ? timestampaddSecond_int64_##T(c, v) : op == 1 ? timestampaddMinute_int64_##T(c, v)              \
+           : op == 2 ? timestampaddHour_int64_##T(c, v) : op == 3 ? timestampaddDay_int64_##T(c, v)                   \
+           : op == 4 ? timestampaddWeek_int64_##T(c, v) : op == 5 ? timestampaddMonth_int64_##T(c, v)                 \
+           : op == 6 ? timestampaddQuarter_int64_##T(c, v) : op == 7 ? timestampaddYear_int64_##T(c, v)               \
+           : op == 8 ? date_add_##T##_int64(v, c) : op == 9 ? date_sub_##T##_int64(v, c)                              \
+           : op == 10 ? date_add_##T##_int32(v, (gdv_int32)c) : date_sub_##T##_int32(v, (gdv_int32)c);                \
+    break;                                                                                                            \
+  }
+      HOST_EACH_MILLIS(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// op: 0..7 timestampdiff{Second, Minute, Hour, Day, Week, Month, Quarter, Year}(a, b), 8 datediff(a, b); date32 (tk 0) has datediff only
+void host_temporal_diff(int tk, int op, const void* av, const void* bv, int* out, long n) {
+  for (long i = 0; i < n; i++) {
+    switch (tk) {
+      case 0: out[i] = datediff_date32_date32(((const gdv_date32*)av)[i], ((const gdv_date32*)bv)[i]); break;
+#define X(K, T)                                                                                                       \
+  case K: {                                                                                                           \
+    const gdv_##T a = ((const gdv_##T*)av)[i], b = ((const gdv_##T*)bv)[i];                                           \
+    out[i] = op == 0 ? timestampdiffSecond_##T##_##T(a, b) : op == 1 ? timestampdiffMinute_##T##_##T(a, b)            \
+           : op == 2 ? timestampdiffHour_##T##_##T(a, b) : op == 3 ? timestampdiffDay_##T##_##T(a, b)                 \
+           : op == 4 ? timestampdiffWeek_##T##_##T(a, b) : op == 5 ? timestampdiffMonth_##T##_##T(a, b)               \
+           : op == 6 ? timestampdiffQuarter_##T##_##T(a, b) : op == 7 ? timestampdiffYear_##T##_##T(a, b)             \
+                     : datediff_##T##_##T(a, b);                                                                      \
+    break;                                                                                                            \
+  }
+      HOST_EACH_MILLIS(X)
+#undef X
+      default: break;
+    }
+  }
+}
+// op: 0 castDATE(date32), 1 castDATE(timestamp), 2 castDATE32(date64), 3 castTIMESTAMP(date32), 4 castTIME(timestamp),
+//     5 castTIMESTAMP(date64), 6 castBIGINT(date64), 7 castBIGINT(timestamp), 8 castDATE(int64), 9 castTIMESTAMP(int64),
+//     10 extractHour(time32), 11 extractMinute(time32), 12 extractSecond(time32); 32-bit types in and out as int32
+void host_temporal_cast(int op, const void* xv, void* outv, long n) {
+  for (long i = 0; i < n; i++) {
+    const bool narrow = op == 0 || op == 3 || op >= 10;   // the argument is date32 / time32
+    const gdv_int32 x32 = narrow ? ((const gdv_int32*)xv)[i] : 0;
+    const gdv_int64 x64 = narrow ? 0 : ((const gdv_int64*)xv)[i];
+    switch (op) {
+      case 0: ((gdv_int64*)outv)[i] = castDATE_date32(x32); break;
+      case 1: ((gdv_int64*)outv)[i] = castDATE_timestamp(x64); break;
+      case 2: ((gdv_int32*)outv)[i] = castDATE32_date64(x64); break;
+      case 3: ((gdv_int64*)outv)[i] = castTIMESTAMP_date32(x32); break;
+      case 4: ((gdv_int32*)outv)[i] = castTIME_timestamp(x64); break;
+      case 5: ((gdv_int64*)outv)[i] = castTIMESTAMP_date64(x64); break;
+      case 6: ((gdv_int64*)outv)[i] = castBIGINT_date64(x64); break;
+      case 7: ((gdv_int64*)outv)[i] = castBIGINT_timestamp(x64); break;
+      case 8: ((gdv_int64*)outv)[i] = castDATE_int64(x64); break;
+      case 9: ((gdv_int64*)outv)[i] = castTIMESTAMP_int64(x64); break;
+      case 10: ((gdv_int64*)outv)[i] = extractHour_time32(x32); break;
+      case 11: ((gdv_int64*)outv)[i] = extractMinute_time32(x32); break;
+      default: ((gdv_int64*)outv)[i] = extractSecond_time32(x32); break;
+    }
+  }
+}
+
 }  // extern "C"
