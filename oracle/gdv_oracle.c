@@ -1449,6 +1449,9 @@ static void eval_function(const node* n, ctx* c, int64_t row0, int cnt, const ui
           out->sp[i] = x; out->sl[i] = keep; out->sm[i] = (uint8_t)xm;
           continue;
         }
+        /* padding to more than 65536 characters is an error: the limit of this backend's pads (a literal length above
+         * it is refused when the projector is made, a per-row one raises on the row that needs the padding) */
+        if (want > 65536) { if (out->valid[i] && (!active || active[i])) c->err |= 4; out->sp[i] = x; out->sl[i] = 0; continue; }
         int64_t pad = want - chars;
         uint8_t* dst = arena_alloc(c, (size_t)xl + (size_t)pad * 4 + 1);
         size_t at = 0;

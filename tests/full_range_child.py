@@ -44,12 +44,14 @@ CHILD = textwrap.dedent("""
         finally:
             lib.gdv_schema_free(sh)
 
-    # packed many to a projector: at most 36 outputs, and on the interpreter as many as one program takes
+    # packed many to a projector: at most 36 outputs, and on the interpreter as many as one program takes (a case may
+    # name its projectors itself: "groups", lists of expression numbers)
     groups = [[]]
     for i in range(len(exprs)):
         if len(groups[-1]) == 36 or (interpreted and groups[-1] and not program_of(groups[-1] + [i])):
             groups.append([])
         groups[-1].append(i)
+    groups = case.get("groups", groups)
     projs = []
     for group in groups:
         if interpreted:
@@ -62,10 +64,14 @@ CHILD = textwrap.dedent("""
         for off, rows in ((0, len(table)), (0, 1), (0, 63), (0, 64), (0, 65), (37, 2000)):
             part = table.slice(off, rows)
             batch = pa.RecordBatch.from_arrays([part.column(n).chunk(0) for n in R.SCHEMA.names], schema=R.SCHEMA)
+            if hasattr(R, "child_batch"):          # a reference whose inputs have a buffer layout that a file does not keep
+                batch = R.child_batch(nulls, batch, off, rows)
             for group, proj in zip(groups, projs):
                 before = lib.gdv_tier0_launches()
                 got = proj.evaluate(batch)
                 evaluations += 1
+                if hasattr(R, "child_after_evaluate"):      # a reference's own assertions on the path the evaluation took
+                    R.child_after_evaluate(case, nulls, group, proj, rows == len(table))
                 if interpreted:
                     assert lib.gdv_tier0_launches() - before == 1, "the evaluation was not interpreted (exactly once)"
                 else:
@@ -74,6 +80,8 @@ CHILD = textwrap.dedent("""
                     want = part.column("e%d" % specs[i]["column"]).chunk(0)
                     what = "%s nulls=%s offset=%d rows=%d" % (specs[i]["label"], nulls, off, rows)
                     try:
+                        if getattr(R, "VALIDATE_OUTPUTS", False):      # (not for date64: full-range values are no whole days)
+                            g.validate(full=True)
                         if "x%d" % specs[i]["column"] in part.column_names:
                             assert_bit_exact_where(g, want, ~np.asarray(part.column("x%d" % specs[i]["column"]).chunk(0)), what)
                         elif specs[i]["ulps"] is None:
@@ -84,6 +92,8 @@ CHILD = textwrap.dedent("""
                             R.assert_class_and_ulp(g, want, specs[i]["ulps"], what)
                     except AssertionError as e:
                         failures.append(str(e))
+    if hasattr(R, "child_extra_passes"):      # further passes of a reference's own (device-resident inputs, selection vectors)
+        evaluations += R.child_extra_passes(gandiva, case, exprs, groups, projs, failures)
     assert not failures, "%d comparisons failed:\\n%s" % (len(failures), "\\n".join(failures[:40]))
     print("FAMILY OK %s: %d expressions, %d projectors, %d evaluations" % (case["family"], len(specs), len(projs), evaluations))
 """)
@@ -114,7 +124,8 @@ def write_case(R, case_dir, name, specs, expected_by_nulls, left_out_by_nulls=No
 ENDED_BADLY = []
 
 
-def run_child(module, case_path, interpreted, timeout=240):
+def run_child(module, case_path, interpreted, timeout=240, extra_env=None):
+    """One fresh child process over a case; `extra_env` is added to the child's environment."""
     assert not ENDED_BADLY, "not started: an earlier child process of the full-range tests " + ENDED_BADLY[0]
     with open(case_path) as f:
         case = json.load(f)
@@ -127,6 +138,7 @@ def run_child(module, case_path, interpreted, timeout=240):
     env.pop("GDV_FORCE_TIER0", None)
     env.pop("GDV_NO_TIER0", None)
     env["GDV_FORCE_TIER0" if interpreted else "GDV_NO_TIER0"] = "1"
+    env.update(extra_env or {})
     try:
         r = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT, module=module), case_path], env=env, capture_output=True, text=True, timeout=timeout)
     except subprocess.TimeoutExpired:

@@ -177,7 +177,27 @@ def py_murmur3_x64_128_h1(data: bytes, seed: int) -> int:
     return h1 - (1 << 64) if h1 >> 63 else h1
 
 
-# ---- full-range operands (tests/test_full_range_numeric*.py) ----------------------------------------------------------
+def py_murmur3_x86_32(data: bytes, seed: int) -> int:
+    """Independent pure-Python MurmurHash3_x86_32 (signed); the seed is taken modulo 2^32."""
+    M = 0xffffffff
+    rotl = lambda v, d: ((v << d) | (v >> (32 - d))) & M
+    h = seed & M
+    nblocks = len(data) // 4
+    for b in range(nblocks):
+        k = int.from_bytes(data[4 * b: 4 * b + 4], "little")
+        k = k * 0xcc9e2d51 & M; k = rotl(k, 15); k = k * 0x1b873593 & M
+        h ^= k; h = rotl(h, 13); h = (h * 5 + 0xe6546b64) & M
+    tail = data[4 * nblocks:]
+    if tail:
+        k = int.from_bytes(tail, "little")
+        k = k * 0xcc9e2d51 & M; k = rotl(k, 15); k = k * 0x1b873593 & M
+        h ^= k
+    h ^= len(data)
+    h ^= h >> 16; h = h * 0x85ebca6b & M; h ^= h >> 13; h = h * 0xc2b2ae35 & M; h ^= h >> 16
+    return h - (1 << 32) if h >> 31 else h
+
+
+# ---- full-range operands (tests/test_full_range_numeric*.py)----------------------------------------------------------
 
 def _np_dtype(t):
     return np.dtype(t.to_pandas_dtype())

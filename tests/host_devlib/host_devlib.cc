@@ -152,6 +152,27 @@ void host_str_int(int fn, const int* off, const unsigned char* data, long size, 
     }
   }
 }
+// the rest of the numbers and compares (tests/test_string_shapes_cpu.py): k is the start of locate / the seed of a hash
+void host_str_int_k(int fn, const int* off, const unsigned char* data, long size, long n, const unsigned char* lit, int litlen,
+                    long long k, long long* out) {
+  HostCol c{off, data, size};
+  unsigned err = 0;
+  gdv_ctx ctx{&err};
+  for (long i = 0; i < n; i++) {
+    const gdv_str s = host_row(c, i), l = host_lit(lit, litlen);
+    switch (fn) {
+      case 0: out[i] = bit_length_utf8(s); break;
+      case 1: out[i] = locate_utf8_utf8_int32(ctx, l, s, (gdv_int32)k); break;
+      case 2: out[i] = strpos_utf8_utf8(ctx, s, l); break;
+      case 3: out[i] = hash32_utf8_int32(s, true, (gdv_int32)k, true); break;
+      case 4: out[i] = hash64_utf8_int64(s, true, k, true); break;
+      case 5: out[i] = not_equal_utf8_utf8(s, l); break;
+      case 6: out[i] = less_than_or_equal_to_utf8_utf8(s, l); break;
+      case 7: out[i] = greater_than_utf8_utf8(s, l); break;
+      default: out[i] = 0; break;
+    }
+  }
+}
 // view-producing functions, materialised with gdv_str_copy the way the byte pass does
 long host_str_view(int fn, const int* off, const unsigned char* data, long size, long n, long long a,
                    long long b, int map, int* out_off, unsigned char* out_data) {

@@ -18,27 +18,8 @@ from oracle import oracle
 NULL = None
 
 
-def _upper(v):
-    return "".join(chr(ord(c) - 32) if "a" <= c <= "z" else c for c in v)
-
-
-def _lower(v):
-    return "".join(chr(ord(c) + 32) if "A" <= c <= "Z" else c for c in v)
-
-
-def _substr(v, start, count=0x7fffffff):
-    if count <= 0 or not v:
-        return ""
-    n = len(v)
-    s = start - 1 if start > 0 else (n + start if start < 0 else 0)
-    if s < 0 or s >= n:
-        return ""
-    return v[s:s + count]
-
-
-def _like(v, pat):
-    rx = "".join(".*" if c == "%" else "." if c == "_" else re.escape(c) for c in pat)
-    return re.fullmatch(rx, v, re.DOTALL) is not None
+# the restatements of upper / lower / substr / like live in tests/string_shapes.py (one copy for every test file)
+from string_shapes import ascii_upper as _upper, ascii_lower as _lower, substr as _substr, like as _like, pad as _pad  # noqa: E402
 
 
 def _and(vals):      # SQL three-valued AND
@@ -120,13 +101,7 @@ def py_eval(node, row):
     if f == "replace":
         return a[0].replace(a[1], a[2]) if a[1] else a[0]
     if f in ("lpad", "rpad"):
-        v, n, fill = a[0], a[1], (a[2] if len(a) == 3 else " ")
-        if v == "" or n <= 0:
-            return ""
-        if len(v) >= n or fill == "":
-            return v[:n] if len(v) > n else v
-        pad = (fill * n)[:n - len(v)]
-        return v + pad if f == "rpad" else pad + v
+        return _pad(a[0], a[1], a[2] if len(a) == 3 else " ", f == "rpad")
     if f == "castVARCHAR":
         return str(a[0])[:a[1]]
     if f == "octet_length":

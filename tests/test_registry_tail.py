@@ -215,14 +215,7 @@ WORDS = ["hello", "WORLD", "mIxEd", "a", "Z", "x1y2", "42", "9lives", "o'neil", 
          "tab\tsep", "two  spaces", " lead", "trail ", "", "ÉCOLE", "straße", "naïve café", "日本語 text", "aéb CÉD", "éx"]
 
 
-def _initcap_by_regex(t):
-    if t is None:
-        return None
-    def word(m):
-        w = m.group(0)
-        head = w[:1].upper() if w[0] < 0x80 else w[:1]
-        return head + w[1:].lower()          # bytes.lower() / .upper() touch ASCII letters only
-    return re.sub(rb"[A-Za-z0-9\x80-\xff]+", word, t.encode()).decode()
+from string_shapes import initcap as _initcap_by_regex  # noqa: E402  (the restatement lives in tests/string_shapes.py)
 
 
 def _initcap_cases(seed, n):

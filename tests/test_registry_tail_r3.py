@@ -166,15 +166,7 @@ def test_oracle_month_differences_match_dateutil_month_arithmetic():
     assert got == [k for _, _, k in kat]
 
 
-def _python_pad(v, n, fill, right):
-    if v is None:
-        return None
-    if v == "" or n <= 0:
-        return ""
-    if len(v) >= n or fill == "":
-        return v[:n] if len(v) > n else v
-    pad = (fill * n)[:n - len(v)]
-    return v + pad if right else pad + v
+from string_shapes import pad as _python_pad  # noqa: E402  (the restatement lives in tests/string_shapes.py)
 
 
 def test_oracle_reverse_pad_and_integer_text_match_python():

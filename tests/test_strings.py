@@ -288,28 +288,7 @@ def _position_exprs(b, s, t):
     return out
 
 
-def _python_positions(vals, subs):
-    """The same expressions in plain Python (str = sequence of characters)."""
-    cols = []
-
-    def col(fn):
-        cols.append([None if v is None else fn(v) for v in vals])
-    for k in (0, 1, 3, 100, -1, -4, -100):
-        col(lambda v, k=k: "" if k == 0 else (v[:k] if k > 0 else v[:max(len(v) + k, 0)]))
-        col(lambda v, k=k: "" if k == 0 else (v[max(len(v) - k, 0):] if k > 0 else v[min(-k, len(v)):]))
-    for k in (0, 2, 7, 1000):
-        col(lambda v, k=k: v[:k])
-    for sub in ("spark", "a", "é", "日本", ""):
-        f = lambda v, sub=sub: 0 if not v or not sub else v.find(sub) + 1
-        col(f)
-        col(f)
-    col(lambda v: 0 if not v else v.find("a", 2) + 1)
-    cols.append([None if v is None or t is None else (0 if not v or not t else v.find(t) + 1)
-                 for v, t in zip(vals, subs)])
-    first = lambda v: 0 if not v else int(np.int8(np.uint8(v.encode()[0])))
-    col(first)
-    col(lambda v: 0 if not v else int(np.int8(np.uint8(v.encode()[0] - 32 if "a" <= v[0] <= "z" else v.encode()[0]))))
-    return cols
+from string_shapes import python_positions as _python_positions  # noqa: E402  (the restatement lives in tests/string_shapes.py)
 
 
 def _position_batch(n, seed):
@@ -381,23 +360,7 @@ def _concat_exprs(b, s, t):
     return out
 
 
-def _python_concat(ss, ts):
-    e = lambda v: "" if v is None else v
-    cols = [[e(s) + e(t) for s, t in zip(ss, ts)],
-            [None if s is None or t is None else s + t for s, t in zip(ss, ts)],
-            [e(s) + " - " + ("" if t is None else _ascii_upper(t)) for s, t in zip(ss, ts)],
-            [None if s is None else s[1:4] + "|" + _ascii_lower(s) for s in ss],
-            [("" if s is None or t is None else s + t) + "." + e(t) + e(t) for s, t in zip(ss, ts)],
-            [e(s) + e(t) + e(s) + e(t) + "日本" for s, t in zip(ss, ts)]]
-    return cols
-
-
-def _ascii_upper(v):
-    return "".join(chr(ord(c) - 32) if "a" <= c <= "z" else c for c in v)
-
-
-def _ascii_lower(v):
-    return "".join(chr(ord(c) + 32) if "A" <= c <= "Z" else c for c in v)
+from string_shapes import python_concat as _python_concat, ascii_upper as _ascii_upper, ascii_lower as _ascii_lower  # noqa: E402,F401
 
 
 def test_oracle_concat_matches_python():
