@@ -447,6 +447,132 @@ GDV_DEV gdv_float64 ceil_float64(gdv_float64 a) { return ceil(a); }
 GDV_DEV gdv_float64 round_float64(gdv_float64 a) { return gdv_round_half_away(a); }
 GDV_DEV gdv_float64 truncate_float64(gdv_float64 a) { return trunc(a); }
 
+// ------------------------------------------------------------------ numeric tail: trigonometry, sign, pmod, round to a
+// scale, shifts, gcd / lcm.  All null-if-null, none takes a context, none raises; integer work is done in unsigned types
+// (no signed overflow, no shift by the width or more).  What is recollection and what was decided: PARITY.md, numeric tail.
+//
+// Trigonometry and angles: the argument is converted to double once, the result is float64.  cot is tan(pi/2 - x) with
+// ONE subtraction from the double nearest pi/2 (the lineage's formula as recalled, not the mathematical cotangent: for
+// large |x| the subtraction absorbs pi/2); degrees / radians are ONE multiplication by the double 180/pi, pi/180.
+#define GDV_PI 3.14159265358979323846
+GDV_DEV gdv_float64 gdv_cot(gdv_float64 x) { return tan(GDV_PI / 2 - x); }
+GDV_DEV gdv_float64 gdv_degrees(gdv_float64 x) { return x * (180.0 / GDV_PI); }
+GDV_DEV gdv_float64 gdv_radians(gdv_float64 x) { return x * (GDV_PI / 180.0); }
+#define GDV_TRIG_FNS(X, T)                                                                                  \
+  X(sin, sin, T) X(cos, cos, T) X(tan, tan, T) X(asin, asin, T) X(acos, acos, T) X(atan, atan, T)           \
+  X(sinh, sinh, T) X(cosh, cosh, T) X(tanh, tanh, T) X(cot, gdv_cot, T) X(degrees, gdv_degrees, T)          \
+  X(radians, gdv_radians, T)
+#define GDV_TRIG(name, f, T) GDV_DEV gdv_float64 name##_##T(gdv_##T a) { return f((gdv_float64)a); }
+GDV_TRIG_FNS(GDV_TRIG, int32) GDV_TRIG_FNS(GDV_TRIG, int64) GDV_TRIG_FNS(GDV_TRIG, float32) GDV_TRIG_FNS(GDV_TRIG, float64)
+GDV_DEV gdv_float64 atan2_float64_float64(gdv_float64 y, gdv_float64 x) { return atan2(y, x); }
+
+// sign: -1, 0 or 1 in the argument's type; +-0 -> +0.0, NaN -> NaN
+GDV_DEV gdv_int32 sign_int32(gdv_int32 a) { return (a > 0) - (a < 0); }
+GDV_DEV gdv_int64 sign_int64(gdv_int64 a) { return (gdv_int64)((a > 0) - (a < 0)); }
+GDV_DEV gdv_float32 sign_float32(gdv_float32 a) { return a != a ? a : a > 0 ? 1.0f : a < 0 ? -1.0f : 0.0f; }
+GDV_DEV gdv_float64 sign_float64(gdv_float64 a) { return a != a ? a : a > 0 ? 1.0 : a < 0 ? -1.0 : 0.0; }
+
+// pmod: the floored modulus (the divisor's sign); a zero divisor returns the dividend, as integer mod does.  The
+// remainder is moved by the divisor only where their signs differ, so the sum cannot leave the type.
+#define GDV_PMOD(T, U)                                                       \
+  GDV_DEV gdv_##T pmod_##T##_##T(gdv_##T a, gdv_##T n) {                     \
+    if (n == 0) return a;                                                    \
+    if (n == -1) return 0;                                                   \
+    const gdv_##T r = a % n;                                                 \
+    if (r != 0 && ((r ^ n) < 0)) return (gdv_##T)((gdv_##U)r + (gdv_##U)n);  \
+    return r;                                                                \
+  }
+GDV_PMOD(int32, uint32) GDV_PMOD(int64, uint64)
+
+// round / truncate of an integer to a scale: scale >= 0 gives the value, scale s < 0 a multiple of 10^-s (round: half away
+// from zero, truncate: toward zero), |s| above 9 / 18 gives 0.  The magnitude is taken unsigned; a result that does not
+// fit wraps modulo 2^w.
+GDV_DEV gdv_uint64 gdv_pow10_u64(int k) {  // k in 0..19
+  gdv_uint64 p = 1;
+  for (int i = 0; i < k; i++) p *= 10u;
+  return p;
+}
+#define GDV_INT_SCALE(T, U, MAXS)                                                                  \
+  GDV_DEV gdv_##T gdv_to_scale_##T(gdv_##T a, gdv_int32 s, bool half) {                            \
+    if (s >= 0) return a;                                                                          \
+    if (s < -(MAXS)) return 0;                                                                     \
+    const gdv_##U p = (gdv_##U)gdv_pow10_u64(-s);                                                  \
+    const gdv_##U mag = a < 0 ? (gdv_##U)0 - (gdv_##U)a : (gdv_##U)a;                              \
+    const gdv_##U r = mag % p;                                                                     \
+    gdv_##U q = mag - r;                                                                           \
+    if (half && r >= p - r) q += p;                                                                \
+    return (gdv_##T)(a < 0 ? (gdv_##U)0 - q : q);                                                  \
+  }                                                                                                \
+  GDV_DEV gdv_##T round_##T(gdv_##T a) { return a; }                                               \
+  GDV_DEV gdv_##T round_##T##_int32(gdv_##T a, gdv_int32 s) { return gdv_to_scale_##T(a, s, true); } \
+  GDV_DEV gdv_##T truncate_##T##_int32(gdv_##T a, gdv_int32 s) { return gdv_to_scale_##T(a, s, false); }
+GDV_INT_SCALE(int32, uint32, 9) GDV_INT_SCALE(int64, uint64, 18)
+
+// round of a float to a scale: trunc(x * m + (x >= 0 ? 0.5 : -0.5)) / m in double, m = the double nearest 10^s from a
+// constant table (-308 <= s <= 308; no pow).  NaN and infinities are returned as they are, and so is x where x * m is
+// not finite or s > 308; s < -308 gives 0.0 with x's sign.  float32: widened first, narrowed once at the end.
+#define GDV_P10_ROW(p) p##0, p##1, p##2, p##3, p##4, p##5, p##6, p##7, p##8, p##9
+#define GDV_P10_TABLE(e)                                                                                              \
+  GDV_P10_ROW(e), GDV_P10_ROW(e##1), GDV_P10_ROW(e##2), GDV_P10_ROW(e##3), GDV_P10_ROW(e##4), GDV_P10_ROW(e##5),      \
+  GDV_P10_ROW(e##6), GDV_P10_ROW(e##7), GDV_P10_ROW(e##8), GDV_P10_ROW(e##9), GDV_P10_ROW(e##10), GDV_P10_ROW(e##11), \
+  GDV_P10_ROW(e##12), GDV_P10_ROW(e##13), GDV_P10_ROW(e##14), GDV_P10_ROW(e##15), GDV_P10_ROW(e##16),                 \
+  GDV_P10_ROW(e##17), GDV_P10_ROW(e##18), GDV_P10_ROW(e##19), GDV_P10_ROW(e##20), GDV_P10_ROW(e##21),                 \
+  GDV_P10_ROW(e##22), GDV_P10_ROW(e##23), GDV_P10_ROW(e##24), GDV_P10_ROW(e##25), GDV_P10_ROW(e##26),                 \
+  GDV_P10_ROW(e##27), GDV_P10_ROW(e##28), GDV_P10_ROW(e##29), e##300, e##301, e##302, e##303, e##304, e##305, e##306, \
+  e##307, e##308
+GDV_DEV gdv_float64 gdv_pow10_f64(gdv_int32 s) {  // s in -308..308
+  static constexpr gdv_float64 kUp[309] = {GDV_P10_TABLE(1e)};
+  static constexpr gdv_float64 kDown[309] = {GDV_P10_TABLE(1e-)};
+  return s >= 0 ? kUp[s] : kDown[-s];
+}
+GDV_DEV gdv_float64 round_float64_int32(gdv_float64 x, gdv_int32 s) {
+  if (!(fabs(x) <= 1.7976931348623157e308)) return x;  // NaN, +-inf
+  if (s > 308) return x;
+  if (s < -308) return copysign(0.0, x);
+  const gdv_float64 m = gdv_pow10_f64(s);
+  const gdv_float64 xm = x * m;
+  if (!(fabs(xm) <= 1.7976931348623157e308)) return x;
+  return trunc(xm + (x >= 0 ? 0.5 : -0.5)) / m;
+}
+GDV_DEV gdv_float32 round_float32_int32(gdv_float32 x, gdv_int32 s) {
+  if (!(fabsf(x) <= 3.40282347e38f)) return x;
+  return (gdv_float32)round_float64_int32((gdv_float64)x, s);
+}
+
+// shifts: the count is taken modulo the width (Java's rule), so negative counts follow from the mask
+#define GDV_SHIFTS(T, U, MASK)                                                                                    \
+  GDV_DEV gdv_##T shift_left_##T##_int32(gdv_##T a, gdv_int32 n) { return (gdv_##T)((gdv_##U)a << (n & MASK)); }  \
+  GDV_DEV gdv_##T shift_right_unsigned_##T##_int32(gdv_##T a, gdv_int32 n) {                                      \
+    return (gdv_##T)((gdv_##U)a >> (n & MASK));                                                                   \
+  }                                                                                                               \
+  GDV_DEV gdv_##T shift_right_##T##_int32(gdv_##T a, gdv_int32 n) { /* arithmetic: the sign fills from the top */ \
+    const gdv_##U fill = a < 0 ? ~(~(gdv_##U)0 >> (n & MASK)) : (gdv_##U)0;                                       \
+    return (gdv_##T)(((gdv_##U)a >> (n & MASK)) | fill);                                                          \
+  }
+GDV_SHIFTS(int32, uint32, 31) GDV_SHIFTS(int64, uint64, 63)
+
+// gcd / lcm over the magnitudes as uint64: the non-negative value, gcd(0, 0) = 0, lcm(0, x) = 0; a result of 2^63 or
+// above wraps.  Binary GCD on count-trailing-zeros: shifts and subtractions, no 64-bit division (a software routine here).
+GDV_DEV gdv_uint64 gdv_gcd_u64(gdv_uint64 a, gdv_uint64 b) {
+  if (a == 0) return b;
+  if (b == 0) return a;
+  const int shift = __builtin_ctzll(a | b);
+  a >>= __builtin_ctzll(a);
+  do {
+    b >>= __builtin_ctzll(b);
+    if (a > b) { const gdv_uint64 t = a; a = b; b = t; }
+    b -= a;
+  } while (b != 0);
+  return a << shift;
+}
+GDV_DEV gdv_uint64 gdv_mag_u64(gdv_int64 a) { return a < 0 ? 0ull - (gdv_uint64)a : (gdv_uint64)a; }
+GDV_DEV gdv_int64 gcd_int64_int64(gdv_int64 a, gdv_int64 b) { return (gdv_int64)gdv_gcd_u64(gdv_mag_u64(a), gdv_mag_u64(b)); }
+GDV_DEV gdv_int64 lcm_int64_int64(gdv_int64 a, gdv_int64 b) {
+  const gdv_uint64 x = gdv_mag_u64(a), y = gdv_mag_u64(b);
+  if (x == 0 || y == 0) return 0;
+  return (gdv_int64)(x / gdv_gcd_u64(x, y) * y);
+}
+
 // ------------------------------------------------------------------ hash
 // Murmur3-derived hashes over the 8-byte image of the value as a double (every numeric
 // type is first converted to double).  A null input hashes to the seed (0 without seed).

@@ -190,6 +190,26 @@ FunctionRegistry::FunctionRegistry() {
   add("pow", {float64(), float64()}, float64(), NullPolicy::kNullIfNull, 0, Sym("power", {float64(), float64()}));
   add("log", {float64(), float64()}, float64(), NullPolicy::kNullIfNull, kNeedsContext);
 
+  // numeric tail: trigonometry and angles (the argument converted to double once), sign, pmod, round / truncate to a
+  // scale, shifts, gcd / lcm.  None raises, so every one has a tier-0 instruction (gdv_tier0_fns.inc).
+  for (auto& t : {int32(), int64(), float32(), float64()}) {
+    for (const char* f : {"sin", "cos", "tan", "asin", "acos", "atan", "sinh", "cosh", "tanh", "cot", "degrees", "radians"})
+      add(f, {t}, float64());
+    add("sign", {t}, t);
+  }
+  add("atan2", {float64(), float64()}, float64());
+  for (auto& t : {int32(), int64()}) {
+    add("pmod", {t, t}, t);
+    add("round", {t}, t);
+    add("round", {t, int32()}, t);
+    add("truncate", {t, int32()}, t);
+    for (const char* f : {"shift_left", "shift_right", "shift_right_unsigned"}) add(f, {t, int32()}, t);
+  }
+  add("round", {float32(), int32()}, float32());
+  add("round", {float64(), int32()}, float64());
+  add("gcd", {int64(), int64()}, int64());
+  add("lcm", {int64(), int64()}, int64());
+
   // hash family: never null, null input hashes to the seed
   std::vector<DataType> hashable = numerics;
   hashable.push_back(boolean());
