@@ -898,6 +898,38 @@ GDV_DEV gdv_date64 castDATE_timestamp(gdv_timestamp t) {
   return gdv_floor_div(t, GDV_MILLIS_IN_DAY) * GDV_MILLIS_IN_DAY;
 }
 
+// The calendar tail: months_between, next_day, add_months (date_trunc('unit', t), next_day(t, 'name') and the extractor
+// names year, month, day ... are rewritten or aliased onto functions above: gdv_node.h, gdv_registry.cc).  None raises.
+// months_between(end, start) -> float64 [Hive's rule, as recalled; NOT rounded to 8 digits: decided]: the month count of
+// the two civil dates; a whole number when the days of month agree or both are the last of their months (the times of
+// day are ignored then), else plus the difference of the days of month and of the times of day in 31-day months.
+// Every step is ONE IEEE double operation in the order written (the kernels are compiled with -ffp-contract=off).  The
+// month count stays below 2^33 on all of int64 milliseconds.
+GDV_DEV gdv_float64 gdv_months_between_f64(gdv_int64 e, gdv_int64 s) {
+  const gdv_ymd a = gdv_civil_from_days(gdv_floor_div(e, GDV_MILLIS_IN_DAY)), b = gdv_civil_from_days(gdv_floor_div(s, GDV_MILLIS_IN_DAY));
+  const gdv_int64 n = (a.y - b.y) * 12 + (a.m - b.m);
+  if (a.d == b.d || (a.d == gdv_last_day_of_month(a.y, a.m) && b.d == gdv_last_day_of_month(b.y, b.m))) return (gdv_float64)n;
+  const gdv_int64 te = gdv_floor_mod(e, GDV_MILLIS_IN_DAY), ts = gdv_floor_mod(s, GDV_MILLIS_IN_DAY);
+  return (gdv_float64)n + ((gdv_float64)(a.d - b.d) + (gdv_float64)(te - ts) / 86400000.0) / 31.0;
+}
+// next_day(t, dow) -> date64: midnight of the first day strictly after t's day whose weekday is dow, in extractDow's
+// numbering (1 = Sunday ... 7 = Saturday); a dow outside 1..7 is reduced by the floored modulus (widened first:
+// INT32_MIN - 1 does not fit).  The product is taken modulo 2^64: within 7 days of INT64_MAX the exact result leaves int64.
+GDV_DEV gdv_date64 gdv_next_day(gdv_int64 v, gdv_int32 dow) {
+  const gdv_int64 day = gdv_floor_div(v, GDV_MILLIS_IN_DAY);
+  const gdv_int64 want = gdv_floor_mod((gdv_int64)dow - 1, 7) + 1, cur = gdv_floor_mod(day + 4, 7) + 1;
+  const gdv_int64 delta = gdv_floor_mod(want - cur, 7);
+  return (gdv_int64)((gdv_uint64)(day + (delta == 0 ? 7 : delta)) * (gdv_uint64)GDV_MILLIS_IN_DAY);
+}
+// add_months(t, n) = timestampaddMonth(n, t), the count second
+#define GDV_CALENDAR_TAIL(T)                                                                                              \
+  GDV_DEV gdv_float64 months_between_##T##_##T(gdv_##T e, gdv_##T s) { return gdv_months_between_f64(e, s); }             \
+  GDV_DEV gdv_date64 next_day_##T##_int32(gdv_##T v, gdv_int32 dow) { return gdv_next_day(v, dow); }                      \
+  GDV_DEV gdv_##T add_months_##T##_int32(gdv_##T v, gdv_int32 n) { return timestampaddMonth_int64_##T((gdv_int64)n, v); } \
+  GDV_DEV gdv_##T add_months_##T##_int64(gdv_##T v, gdv_int64 n) { return timestampaddMonth_int64_##T(n, v); }
+GDV_CALENDAR_TAIL(date64)
+GDV_CALENDAR_TAIL(timestamp)
+
 // ------------------------------------------------------------------ decimal128
 // Arrow decimal128 = 128-bit two's complement integer + (precision, scale) in the type.
 // Precision and scale of the operands and of the result are PLAN constants: the planner passes

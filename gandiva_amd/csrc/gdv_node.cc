@@ -1,6 +1,7 @@
 #include "gdv_node.h"
 
 #include <algorithm>
+#include <cctype>
 
 #include <cstdio>
 #include <cstring>
@@ -295,7 +296,38 @@ bool PlainRegexLiteral(const std::string& t) {
     if (std::strchr("\\^$.|?*+()[]{}%_", ch) != nullptr || ch == 0) return false;
   return true;
 }
+
+// the day names of next_day(t, 'name'), 1 = Sunday ... 7 = Saturday as extractDow counts, and the units of date_trunc('unit', t)
+const char* const kDayNames[7][3] = {{"SU", "SUN", "SUNDAY"}, {"MO", "MON", "MONDAY"}, {"TU", "TUE", "TUESDAY"}, {"WE", "WED", "WEDNESDAY"},
+                                     {"TH", "THU", "THURSDAY"}, {"FR", "FRI", "FRIDAY"}, {"SA", "SAT", "SATURDAY"}};
+const char* const kTruncUnits[] = {"Second", "Minute", "Hour", "Day", "Week", "Month", "Quarter", "Year", "Decade", "Century", "Millennium"};
+
+bool EqualsIgnoringAsciiCase(const std::string& a, const char* b) {
+  size_t i = 0;
+  for (; i < a.size() && b[i]; i++)
+    if (std::toupper(static_cast<unsigned char>(a[i])) != std::toupper(static_cast<unsigned char>(b[i]))) return false;
+  return i == a.size() && !b[i];
+}
+
+bool IsCalendarTime(const DataType& t) { return t.id == kDate64 || t.id == kTimestamp; }
+// next_day(t, utf8) / date_trunc(utf8, t): the position of the text argument, or -1
+int CalendarNameArg(const std::string& name, const NodeVector& kids) {
+  if (kids.size() != 2 || !kids[0] || !kids[1]) return -1;
+  if (name == "next_day" && IsCalendarTime(kids[0]->return_type()) && kids[1]->return_type().id == kString) return 1;
+  if (name == "date_trunc" && kids[0]->return_type().id == kString && IsCalendarTime(kids[1]->return_type())) return 0;
+  return -1;
+}
 }  // namespace
+
+std::string CalendarNameRefusal(const FunctionNode& n) {
+  if (CalendarNameArg(n.name(), n.children()) < 0) return "";
+  if (n.name() == "next_day")
+    return "Function " + n.ToString() + " not supported yet: the HIP backend takes next_day with a LITERAL day name only, in any "
+           "letter case and untrimmed: SU MO TU WE TH FR SA, SUN MON TUE WED THU FRI SAT, SUNDAY MONDAY TUESDAY WEDNESDAY THURSDAY "
+           "FRIDAY SATURDAY (or the day's number as int32, 1 = Sunday, per row or literal). ";
+  return "Function " + n.ToString() + " not supported yet: the HIP backend takes date_trunc with a LITERAL unit only, in any "
+         "letter case and untrimmed: second minute hour day week month quarter year decade century millennium. ";
+}
 
 NodePtr MakeFunctionNode(std::string name, NodeVector children, DataType ret) {
   auto literal_text = [&](size_t i, std::string* out) {
@@ -320,6 +352,28 @@ NodePtr MakeFunctionNode(std::string name, NodeVector children, DataType ret) {
   if (name == "regexp_replace" && children.size() == 3 && literal_text(1, &pat) && literal_text(2, &to) &&
       PlainRegexLiteral(pat) && to.find('\\') == std::string::npos)
     return std::make_shared<FunctionNode>("replace", std::move(children), ret);
+  // next_day(t, 'name') -> next_day(t, int32 day number); date_trunc('unit', t) -> date_trunc_<Unit>(t).  A NULL literal
+  // gives add_months / next_day over a NULL int32, whose every row is null; any other text stays as it is and is refused
+  // at Make (CalendarNameRefusal).
+  const int text_arg = CalendarNameArg(name, children);
+  if (text_arg >= 0 && children[text_arg]->kind() == NodeKind::kLiteral) {
+    auto& l = static_cast<const LiteralNode&>(*children[text_arg]);
+    Literal v;
+    v.is_null = l.is_null();
+    if (name == "next_day") {
+      for (int d = 0; d < 7 && !v.is_null && v.lo == 0; d++)
+        for (const char* form : kDayNames[d])
+          if (EqualsIgnoringAsciiCase(l.value().bytes, form)) v.lo = d + 1;
+      if (v.is_null || v.lo != 0)
+        return std::make_shared<FunctionNode>("next_day", NodeVector{children[0], std::make_shared<LiteralNode>(int32(), v)}, ret);
+    } else if (v.is_null) {
+      return std::make_shared<FunctionNode>("add_months", NodeVector{children[1], std::make_shared<LiteralNode>(int32(), v)}, ret);
+    } else {
+      for (const char* unit : kTruncUnits)
+        if (EqualsIgnoringAsciiCase(l.value().bytes, unit))
+          return std::make_shared<FunctionNode>(std::string("date_trunc_") + unit, NodeVector{children[1]}, ret);
+    }
+  }
   return std::make_shared<FunctionNode>(std::move(name), std::move(children), ret);
 }
 

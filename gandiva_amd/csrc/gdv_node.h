@@ -87,7 +87,14 @@ class FunctionNode : public Node {
 // where lit is a non-empty literal without regular-expression or LIKE metacharacters and `to` holds no backslash
 // (RE2 rewrite syntax).  Anything else stays a regexp_* node: regexp_like / regexp_matches are compiled by the planner
 // (gdv_regex.h), regexp_replace beyond a literal pattern is refused there with CodeGenError.
+// The calendar names are resolved here too, so that the kernel and the tier-0 program are those of the target:
+//   next_day(t, 'name')    ->  next_day(t, int32 n)     name: SU / SUN / SUNDAY ... SA / SAT / SATURDAY, n = 1 (Sunday) .. 7
+//   date_trunc('unit', t)  ->  date_trunc_<Unit>(t)     unit: second minute hour day week month quarter year decade century millennium
+// over date64 / timestamp, ASCII, any letter case, nothing trimmed.  A NULL literal becomes a call with a NULL int32
+// count (every row null).  Any other literal and a per-row name or unit stay as they are: Make refuses them with the
+// CodeGenError that CalendarNameRefusal words (it returns "" for every other node).
 NodePtr MakeFunctionNode(std::string name, NodeVector children, DataType ret);
+std::string CalendarNameRefusal(const FunctionNode& n);
 
 class IfNode : public Node {
  public:

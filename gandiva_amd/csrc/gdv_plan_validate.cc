@@ -45,6 +45,9 @@ Status ValidateFunction(const Schema& schema, const FunctionNode& n) {
   const FunctionDef* def = nullptr;
   DataType ret;
   if (!ResolveFunction(n, &def, &ret)) {
+    // next_day(t, text) / date_trunc(text, t) that was no literal name when the node was built
+    const std::string refusal = CalendarNameRefusal(n);
+    if (!refusal.empty()) return Status::CodeGenError(refusal);
     return Status::ValidationError("Function " + n.ToString() + " not supported yet. ");
   }
   if (ret != n.return_type()) {

@@ -266,7 +266,23 @@ FunctionRegistry::FunctionRegistry() {
     }
     add("datediff", {t, t}, int32());
     add("date_diff", {t, t}, int32(), NullPolicy::kNullIfNull, 0, Sym("datediff", {t, t}));
+    // the calendar tail: none raises, so each is one tier-0 instruction.  next_day(t, 'name') and date_trunc('unit', t) are
+    // no signatures of their own: a literal name or unit is rewritten when the node is built (gdv_node.h), onto
+    // next_day(t, int32) and date_trunc_<Unit>(t); anything else is refused at Make (gdv_plan_validate.cc)
+    add("months_between", {t, t}, float64());
+    add("next_day", {t, int32()}, date64());
+    add("add_months", {t, int32()}, t);
+    add("add_months", {t, int64()}, t);
   }
+  // the names a SQL user writes for the extractors: the same symbol, so the same kernel and the same tier-0 instruction
+  const std::pair<const char*, const char*> date_names[] = {
+      {"year", "extractYear"}, {"month", "extractMonth"}, {"day", "extractDay"}, {"dayofmonth", "extractDay"},
+      {"dayofyear", "extractDoy"}, {"dayofweek", "extractDow"}, {"quarter", "extractQuarter"}};
+  const std::pair<const char*, const char*> time_names[] = {{"hour", "extractHour"}, {"minute", "extractMinute"}, {"second", "extractSecond"}};
+  for (auto& t : {date32(), date64(), timestamp()})
+    for (auto& n : date_names) add(n.first, {t}, int64(), NullPolicy::kNullIfNull, 0, Sym(n.second, {t}));
+  for (auto& t : {date32(), date64(), timestamp(), time32()})
+    for (auto& n : time_names) add(n.first, {t}, int64(), NullPolicy::kNullIfNull, 0, Sym(n.second, {t}));
   // round 5: to_date(text, 'pattern'[, suppress_errors]) — the holder's pattern is compiled by the planner;
   // to_timestamp / to_time over numbers (seconds since the epoch)
   add("to_date", {utf8(), utf8()}, date64(), NullPolicy::kNullInternal, kNeedsContext | kDateFormatArg, "gdv_parse_date");

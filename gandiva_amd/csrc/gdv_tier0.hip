@@ -141,14 +141,31 @@ __device__ __forceinline__ gdv_uint64 RetF64(gdv_float64 r) { return FromF64(r);
 
 // kCall1 / kCall2: the device library's function of that id, on the operands' slots.  Out of line: one copy of the
 // calendar and libm code, none of it in the interpreter loop's register budget.
-__device__ __noinline__ gdv_uint64 Call(int fn, gdv_uint64 x, gdv_uint64 y) {
+// In PARTS of kCallPart ids each, and no part may come near 128 KiB of code: past the reach of a short branch the
+// compiler expands the long ones through s[30:31], the registers that hold this leaf function's return address, and a
+// call that takes such a branch never returns (seen when the one switch over all ids reached 140 760 bytes: every
+// function of a low id hung the interpreter).  tests/test_calendar_tail_cpu.py reads the sizes from the assembly.
+constexpr int kCallPart = 64;
+template <int PART>
+__device__ __noinline__ gdv_uint64 CallPart(int fn, gdv_uint64 x, gdv_uint64 y) {
+  constexpr int lo = PART * kCallPart, hi = lo + kCallPart;  // (a case outside the part folds away)
   switch (fn) {
-#define GDV_T0_F1(sym, R, A) case kFn_##sym: return Ret##R(sym(Arg##A(x)));
-#define GDV_T0_F2(sym, R, A, B) case kFn_##sym: return Ret##R(sym(Arg##A(x), Arg##B(y)));
+#define GDV_T0_F1(sym, R, A) case kFn_##sym: if (kFn_##sym >= lo && kFn_##sym < hi) return Ret##R(sym(Arg##A(x))); break;
+#define GDV_T0_F2(sym, R, A, B) case kFn_##sym: if (kFn_##sym >= lo && kFn_##sym < hi) return Ret##R(sym(Arg##A(x), Arg##B(y))); break;
 #include "gdv_tier0_fns.inc"
 #undef GDV_T0_F1
 #undef GDV_T0_F2
-    default: return 0;
+    default: break;
+  }
+  return 0;
+}
+static_assert(kNumFns <= 4 * kCallPart, "a fifth part of the call switch");
+__device__ __forceinline__ gdv_uint64 Call(int fn, gdv_uint64 x, gdv_uint64 y) {
+  switch (fn / kCallPart) {
+    case 0: return CallPart<0>(fn, x, y);
+    case 1: return CallPart<1>(fn, x, y);
+    case 2: return CallPart<2>(fn, x, y);
+    default: return CallPart<3>(fn, x, y);
   }
 }
 
