@@ -47,6 +47,12 @@ class gdv_filter_batch_t(C.Structure):
                 ("out_indices", C.c_void_p), ("max_slots", C.c_int64)]
 
 
+class gdv_filter_project_batch_t(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("cols", C.POINTER(gdv_column_t)), ("num_cols", C.c_int),
+                ("outs", C.POINTER(gdv_out_column_t)), ("num_outs", C.c_int),
+                ("out_indices", C.c_void_p), ("max_slots", C.c_int64)]
+
+
 class gdv_selection_t(C.Structure):
     _fields_ = [("mode", C.c_int32), ("indices", C.c_void_p), ("num_slots", C.c_int64)]
 
@@ -109,6 +115,9 @@ PROTOTYPES = [
     ("gdv_filter_project_num_outputs", C.c_int, [_P]),
     ("gdv_filter_project_output_type", gdv_type_t, [_P, C.c_int]),
     ("gdv_filter_project_evaluate", C.c_int, [_P, C.c_int64, C.POINTER(gdv_column_t), C.c_int, C.POINTER(gdv_out_column_t), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_int, _P, C.c_uint32]),
+    ("gdv_filter_project_evaluate_many", C.c_int, [_P, C.POINTER(gdv_filter_project_batch_t), C.c_int, C.POINTER(C.c_int64), _P, _P, C.c_uint32]),
+    ("gdv_filter_project_small_batch_rows", C.c_int64, [_P]),
+    ("gdv_filter_project_plan_text", _P, [_P, _P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("gdv_filter_project_dump_ir", _P, [_P]),
     ("gdv_filter_project_kernel_shape", C.c_int, [_P]),
     ("gdv_filter_project_set_tuning", C.c_int, [_P, C.c_char_p, C.c_int64]),

@@ -261,6 +261,23 @@ int gdv_precompile_filter_project(const gdv_schema_t* schema, gdv_expression_t* 
   return Check(PrecompileFilterProject(schema->fields, condition->expr, ex, mode));
   });
 }
+char* gdv_filter_project_plan_text(const gdv_schema_t* schema, gdv_expression_t* condition, gdv_expression_t* const* exprs,
+                                   int num_exprs, int index_mode, int shape, int request_small, int compile) {
+  char* out = nullptr;
+  (void)Guarded([&]() -> int {
+  if (!schema || !condition || !condition->expr || !exprs || num_exprs <= 0) return Fail(Status::Invalid("null argument"));
+  SelectionMode mode;
+  if (!ToSelectionMode(index_mode, &mode)) return Fail(Status::Invalid("bad selection mode"));
+  std::vector<ExpressionPtr> ex;
+  if (!CollectExprs(exprs, num_exprs, &ex)) return Fail(Status::Invalid("Expression cannot be null"));
+  std::string text;
+  Status st = FilterProjectPlanText(schema->fields, condition->expr, ex, mode, shape, request_small != 0, compile != 0, &text);
+  if (!st.ok()) return Fail(st);
+  out = DupString(text);
+  return GDV_OK;
+  });
+  return out;
+}
 int gdv_precompile_filter(const gdv_schema_t* schema, gdv_expression_t* condition) {
   return Guarded([&]() -> int {
   if (!schema || !condition || !condition->expr) return Fail(Status::Invalid("null argument"));

@@ -321,6 +321,35 @@ int gdv_filter_project_evaluate(const gdv_filter_project_t* fp, int64_t num_rows
                                 static_cast<hipStream_t>(stream), flags, num_selected_device));
   });
 }
+int gdv_filter_project_evaluate_many(const gdv_filter_project_t* fp, const gdv_filter_project_batch_t* batches,
+                                     int num_batches, int64_t* num_selected, void* num_selected_device, void* stream,
+                                     uint32_t flags) {
+  return Guarded([&]() -> int {
+  if (!fp) return Fail(Status::Invalid("null filter-project"));
+  if (num_batches < 0 || (num_batches > 0 && !batches)) return Fail(Status::Invalid("null batch list"));
+  std::vector<std::vector<ColumnBuffers>> cols(num_batches);
+  std::vector<std::vector<OutputBuffers>> outs(num_batches);
+  std::vector<FilterProject::BatchView> views(num_batches);
+  for (int b = 0; b < num_batches; b++) {
+    const gdv_filter_project_batch_t& g = batches[b];
+    if ((g.num_cols > 0 && !g.cols) || (g.num_outs > 0 && !g.outs))
+      return Fail(Status::Invalid("batch " + std::to_string(b) + ": null column array"));
+    cols[b] = ToColumns(g.cols, g.num_cols);
+    outs[b] = ToOutputs(g.outs, g.num_outs);
+    for (auto& o : outs[b]) { o.offsets = nullptr; o.offsets_size = 0; }  // fixed-width outputs only, as the one-batch call
+    views[b].num_rows = g.num_rows;
+    views[b].cols = cols[b].data();
+    views[b].num_cols = g.num_cols;
+    views[b].outs = outs[b].data();
+    views[b].num_outs = g.num_outs;
+    views[b].out_indices = g.out_indices;
+    views[b].max_slots = g.max_slots;
+  }
+  return Check(fp->fp->EvaluateMany(views.data(), num_batches, num_selected, num_selected_device,
+                                    static_cast<hipStream_t>(stream), flags));
+  });
+}
+int64_t gdv_filter_project_small_batch_rows(const gdv_filter_project_t* fp) { return fp ? fp->fp->SmallBatchRows() : 0; }
 char* gdv_filter_project_dump_ir(const gdv_filter_project_t* fp) { return fp ? DupString(fp->fp->DumpIR()) : nullptr; }
 int gdv_filter_project_kernel_shape(const gdv_filter_project_t* fp) { return fp ? fp->fp->which_kernel() : -1; }
 int gdv_filter_project_set_tuning(gdv_filter_project_t* fp, const char* key, int64_t value) {

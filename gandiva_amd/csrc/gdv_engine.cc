@@ -435,4 +435,20 @@ Status PrecompileFilterProject(const Schema& schema, const ExpressionPtr& condit
   return Status::OK();
 }
 
+Status FilterProjectPlanText(const Schema& schema, const ExpressionPtr& condition, const std::vector<ExpressionPtr>& exprs,
+                             SelectionMode index_mode, int shape, bool with_small, bool compile, std::string* text) {
+  KernelPlan plan;
+  GDV_RETURN_NOT_OK(PlanFilterProject(schema, condition, exprs, index_mode, CodegenOptions::FromEnv(), &plan, with_small));
+  const KernelPlan* which = shape == 0 ? &plan : shape == 1 ? plan.exact.get() : shape == 2 ? plan.small.get() : nullptr;
+  if (shape < 0 || shape > 2) return Status::Invalid("fused filter-project: shapes are 0 (main), 1 (direct), 2 (small)");
+  if (which == nullptr)
+    return Status::CodeGenError(shape == 2 ? "fused filter-project: the plan has no small shape" : "fused filter-project: the plan has one shape only");
+  if (compile) {
+    std::vector<char> code;
+    GDV_RETURN_NOT_OK(Runtime::Get().CompileToCodeObject(which->source, which->kernel_name, &code));
+  }
+  *text = which->source;
+  return Status::OK();
+}
+
 }  // namespace gdv

@@ -81,6 +81,8 @@ struct PlanDeviceState {
   const CompiledKernel* kernel_pre = nullptr;  // wave-shaped plans: the pre-pass kernel
   // the exact variant of a wave-shaped plan (main + pre-pass), compiled when a batch first needs it
   std::atomic<const CompiledKernel*> kernel_exact{nullptr}, kernel_pre_exact{nullptr};
+  // the small shape of a fused filter-project (plan.small), compiled when a list of small batches first needs it
+  std::atomic<const CompiledKernel*> kernel_small{nullptr};
   DeviceBuffer consts, consts_pre;  // string literals / patterns / IN tables (gdv_args::aux0)
 };
 class PlanDeviceStates {
@@ -311,6 +313,26 @@ class FilterProject {
                   void* out_indices, int64_t max_slots, int64_t* num_selected, MemKind mem, hipStream_t stream,
                   uint32_t flags = 0, void* count_out = nullptr) const;
 
+  // Many small HBM-resident batches in ONE launch: every batch is filtered and projected by one workgroup that walks
+  // its workgroup tiles in row order (plan_.small: the windowed body without look-back, ticket or granules; the
+  // workgroup zeroes its own bitmaps, so nothing but the argument table and the kernel is enqueued).  Counts as
+  // Filter::EvaluateMany delivers them.  A batch above SmallBatchRows(num_batches), a plan without the small shape, a table
+  // that does not fit the pinned block, more than 65535 batches or "small" = 0: batch by batch through Evaluate.
+  struct BatchView {
+    int64_t num_rows = 0;
+    const ColumnBuffers* cols = nullptr;
+    int num_cols = 0;
+    OutputBuffers* outs = nullptr;  // sized for num_rows rows, as Evaluate asks
+    int num_outs = 0;
+    void* out_indices = nullptr;    // null when index_mode is kNone
+    int64_t max_slots = 0;
+  };
+  Status EvaluateMany(const BatchView* batches, int num_batches, int64_t* counts_host, void* counts_device,
+                      hipStream_t stream, uint32_t flags) const;
+  // rows per batch up to which a list of nb batches runs in one launch: what one workgroup is given for one batch,
+  // times nb, at most 2^17 (0: the plan has no small shape)
+  int64_t SmallBatchRows(int nb = 1) const;
+
   const Schema& schema() const { return schema_; }
   const KernelPlan& plan() const { return plan_; }
   int num_outputs() const { return static_cast<int>(plan_.output_types.size()); }
@@ -319,9 +341,15 @@ class FilterProject {
   std::string DumpIR() const { return plan_.ir; }
   int which_kernel() const;
   // "kernel" (-1 follow the selectivity, 0 windowed, 1 direct): pin the shape (tests, measurements)
+  // "small" (0 / 1, default 1): 0 sends EvaluateMany batch by batch through Evaluate
+  // "small_rows" (0 .. 2^17, default 0 = SmallBatchRows' rule): the row cap of the one-launch path (measurements)
   Status SetTuning(const std::string& key, int64_t value);
 
  private:
+  // the argument checks of EvaluateFused for batch b of a list (device buffers), before anything is enqueued
+  Status CheckBatch(const BatchView& v, int b) const;
+  std::atomic<bool> small_{true};
+  std::atomic<int64_t> small_rows_{0};  // "small_rows": the row cap to use instead of the rule's (0: the rule; measurements)
   // the kernel launch of one evaluation; *stalled = the look-back gave up (the outputs are not complete)
   Status EvaluateFused(int64_t num_rows, const ColumnBuffers* cols, int num_cols, OutputBuffers* outs, int num_outs,
                        void* out_indices, int64_t max_slots, int64_t* num_selected, MemKind mem, hipStream_t stream,
@@ -361,5 +389,10 @@ Status Tier0Describe(const Schema& schema, const std::vector<ExpressionPtr>& exp
                      SelectionMode mode = SelectionMode::kNone);
 Status PrecompileFilterProject(const Schema& schema, const ExpressionPtr& condition,
                                const std::vector<ExpressionPtr>& exprs, SelectionMode index_mode);
+// The kernel text of one shape of a fused plan, no device: 0 the main kernel (windowed where the plan has that shape),
+// 1 the direct kernel behind a windowed one, 2 the small kernel; planned with or without the small shape; `compile`
+// also compiles that text for gfx950.  CodeGenError when the plan has no such shape.
+Status FilterProjectPlanText(const Schema& schema, const ExpressionPtr& condition, const std::vector<ExpressionPtr>& exprs,
+                             SelectionMode index_mode, int shape, bool with_small, bool compile, std::string* text);
 
 }  // namespace gdv

@@ -32,6 +32,8 @@ Status FilterProject::Make(const Schema& schema, const ExpressionPtr& condition,
 
 Status FilterProject::SetTuning(const std::string& key, int64_t value) {
   if (key == "kernel" && value >= -1 && value <= 1) pinned_kernel_.store(static_cast<int>(value));
+  else if (key == "small" && value >= 0 && value <= 1) small_.store(value != 0);
+  else if (key == "small_rows" && value >= 0 && value <= (int64_t{1} << 17)) small_rows_.store(value);
   else return Status::Invalid("FilterProject tuning: unknown key or value out of range: " + key);
   return Status::OK();
 }
@@ -60,6 +62,164 @@ Status FilterProject::Evaluate(int64_t num_rows, const ColumnBuffers* cols, int 
   // in index order): the launch is over, its outputs are not complete.  Round 4 returned ExecutionError here; the
   // reference's own chain gives the same results without any cross-workgroup wait.
   return EvaluateChain(num_rows, cols, num_cols, outs, num_outs, out_indices, max_slots, num_selected, mem, stream, count_out);
+}
+
+// ------------------------------------------------------------------ many small batches, one launch
+
+// 2^15 rows of a two-int64 predicate: the bytes ONE workgroup is given for one batch.  MEASURED, MI355X,
+// profiles/filter_project_small_batches.txt (tools/small_batch_bench fp, 256 batches per round, ~12 % selected): one
+// batch per call through the by-value entry beats the one-batch call (memsets + look-back kernel + publish-count kernel)
+// up to ~43K rows of the K2F plan (28 bytes per row: 1.2 MB) and ~10K rows of the five-expression threshold plan (62 bytes
+// per row: 0.63 MB); 512 KiB is below both.  (The filter's own rule — 2^17 rows x 16 bytes = 2 MiB — is four times that:
+// a fused plan does more per byte than a predicate.)
+static constexpr int64_t kSmallBatchBytes = int64_t{1} << 19;
+
+int64_t FilterProject::SmallBatchRows(int nb) const {
+  if (plan_.small == nullptr || nb < 1) return 0;
+  if (const int64_t pinned = small_rows_.load(std::memory_order_relaxed)) return pinned;  // (measurements: "small_rows")
+  // Filter::SmallBatchRows' rule — no more rows than one workgroup gets through in about the time the multi-launch
+  // path needs to start, never above 2^17 — scaled by the bytes a row moves: one CU has ~1/256 of the chip's
+  // bandwidth, and a fused plan reads and writes wider rows than a predicate does.
+  int row_bytes = IndexWidth(plan_.mode);
+  for (size_t k = 0; k < plan_.input_fields.size(); k++)
+    if (plan_.input_needs_values[k]) row_bytes += std::max(1, schema_[plan_.input_fields[k]].type.byte_width());
+  for (const DataType& t : plan_.output_types) row_bytes += t.id == kBool ? 1 : t.byte_width();
+  // A list of nb batches: the workgroups run side by side (two per CU), so the launch takes about as long as its
+  // biggest batch, while the batch-by-batch path takes nb times its start-up: nb times the rows still win.  (Same run:
+  // 256 batches of 65536 rows, 1.7-2.6 us per batch in one launch against 75-105 batch by batch.)
+  return std::min<int64_t>(kSmallBatchBytes / std::max(16, row_bytes) * nb, int64_t{1} << 17);
+}
+
+Status FilterProject::CheckBatch(const BatchView& v, int b) const {
+  const std::string where = "batch " + std::to_string(b) + ": ";
+  if (v.num_rows < 0) return Status::Invalid(where + "negative row count");
+  if (v.num_outs != num_outputs() || (v.num_outs > 0 && v.outs == nullptr))
+    return Status::Invalid(where + "number of output buffers does not match the number of expressions");
+  const int w = IndexWidth(plan_.mode);
+  if (w != 0) {
+    if (v.out_indices == nullptr && v.num_rows > 0) return Status::Invalid(where + "Selection vector cannot be null");
+    if (v.max_slots < v.num_rows)
+      return Status::Invalid(where + "Selection vector too small: max slots " + std::to_string(v.max_slots) + " < rows " +
+                             std::to_string(v.num_rows));
+    if (w == 2 && v.num_rows > 65536) return Status::Invalid(where + "uint16 selection vector cannot address " + std::to_string(v.num_rows) + " rows");
+    if (w == 4 && v.num_rows > (int64_t(1) << 32)) return Status::Invalid(where + "uint32 selection vector cannot address " + std::to_string(v.num_rows) + " rows");
+  }
+  if (v.num_rows == 0) return Status::OK();  // (none of its buffers is touched)
+  for (int e = 0; e < v.num_outs; e++) {
+    const int64_t vbytes = Projector::ValidityBytes(v.num_rows), dbytes = Projector::DataBytes(plan_.output_types[e], v.num_rows);
+    if (v.outs[e].validity == nullptr || v.outs[e].data == nullptr || v.outs[e].validity_size < vbytes || v.outs[e].data_size < dbytes)
+      return Status::Invalid(where + "output buffer " + std::to_string(e) + " too small (device buffers need 8-byte word granularity: " +
+                             std::to_string(vbytes) + " validity bytes, " + std::to_string(dbytes) + " data bytes)");
+  }
+  return Status::OK();
+}
+
+static Status EnsureSmall(const KernelPlan& plan, const PlanDeviceState* dev, Runtime& rt) {
+  PlanDeviceState* d = const_cast<PlanDeviceState*>(dev);
+  if (d->kernel_small.load() == nullptr) {
+    const CompiledKernel* k = nullptr;
+    GDV_RETURN_NOT_OK(rt.GetKernel(plan.small->source, plan.small->kernel_name, &k));
+    if (k->function_small == nullptr || k->function_small1 == nullptr)
+      return Status::ExecutionError("internal: the small fused kernel has no multi-batch entry points");
+    d->kernel_small.store(k);
+  }
+  return Status::OK();
+}
+
+Status FilterProject::EvaluateMany(const BatchView* batches, int nb, int64_t* counts_host, void* counts_device,
+                                   hipStream_t stream, uint32_t flags) const {
+  if (nb <= 0) return Status::OK();
+  if (batches == nullptr) return Status::Invalid("null batch list");
+  if (counts_host == nullptr && counts_device == nullptr) return Status::Invalid("no place for the selected-row counts");
+  for (int b = 0; b < nb; b++) GDV_RETURN_NOT_OK(CheckBatch(batches[b], b));
+  Runtime& rt = Runtime::Get();
+  GDV_RETURN_NOT_OK(rt.EnsureDevice());
+  const PlanDeviceState* dev = nullptr;
+  GDV_RETURN_NOT_OK(states_.Get(plan_, &dev));
+  const int64_t cap_rows = SmallBatchRows(nb);
+  const size_t stride = static_cast<size_t>(plan_.layout.total());
+  bool fused = cap_rows > 0 && nb <= 65535 && stride * static_cast<size_t>(nb) <= Runtime::kPinnedBlock / 2 &&
+               small_.load(std::memory_order_relaxed);
+  for (int b = 0; fused && b < nb; b++) fused = batches[b].num_rows <= cap_rows;
+  if (!fused) {
+    for (int b = 0; b < nb; b++) {
+      const BatchView& v = batches[b];
+      int64_t count = 0;
+      GDV_RETURN_NOT_OK(Evaluate(v.num_rows, v.cols, v.num_cols, v.outs, v.num_outs, v.out_indices, v.max_slots, &count,
+                                 MemKind::kDevice, stream, flags,
+                                 counts_device != nullptr ? static_cast<char*>(counts_device) + 8 * b : nullptr));
+      if (counts_host != nullptr) counts_host[b] = count;
+    }
+    return Status::OK();
+  }
+  GDV_RETURN_NOT_OK(EnsureSmall(plan_, dev, rt));
+  const CompiledKernel& kernel = *dev->kernel_small.load();
+  // scratch: [argument table | error word | counts (int64 per batch)] — no look-back granules, no ticket: one
+  // workgroup owns a batch; no memset of the output bitmaps: the workgroup zeroes them itself
+  size_t scratch = (stride * nb + 255) & ~size_t{255};
+  const size_t err_off = scratch;
+  scratch += 256;
+  const size_t cnt_off = scratch;
+  scratch += (static_cast<size_t>(nb) * 8 + 255) & ~size_t{255};
+  DeviceBuffer block;
+  GDV_RETURN_NOT_OK(block.Allocate(scratch));
+  char* const base = block.as<char>();
+  // one batch: its argument block goes by value; several: a table, staged through a pinned block
+  const bool by_value = nb == 1;
+  std::vector<char> one(by_value ? stride : 0);
+  PinnedLease lease(rt);
+  if (!by_value) GDV_RETURN_NOT_OK(lease.Acquire(stride * static_cast<size_t>(nb)));
+  char* const pin = by_value ? one.data() : lease.get();
+  StreamDrain drain{stream, false};  // armed once something is enqueued: error returns wait before the blocks go back
+  Staging st;
+  for (int b = 0; b < nb; b++) {
+    const BatchView& v = batches[b];
+    ArgBlock args(plan_.layout);
+    if (v.num_rows > 0) {  // (a 0-row batch: its workgroup stores the count 0 and touches nothing else)
+      GDV_RETURN_NOT_OK(BindInputs(plan_, schema_, v.cols, v.num_cols, v.num_rows, MemKind::kDevice, stream, &args, &st));
+      if (!st.buffers.empty()) return Status::Invalid("internal: staged input in a multi-batch evaluation");
+      for (int e = 0; e < v.num_outs; e++) {
+        args.SetOutData(e, v.outs[e].data);
+        args.SetOutValid(e, v.outs[e].validity);
+      }
+      args.SetPtr(ArgLayout::kOffSel, v.out_indices);
+    }
+    BindLiterals(plan_, dev->consts, &args);
+    args.Set64(ArgLayout::kOffN, static_cast<uint64_t>(v.num_rows));
+    args.SetPtr(ArgLayout::kOffErr, base + err_off);
+    args.SetPtr(ArgLayout::kOffAux2, base + cnt_off + 8 * b);
+    std::memcpy(pin + stride * b, args.data(), stride);
+  }
+  EvalTrace trace("filter-project-small", plan_.small->kernel_name + (by_value ? "_small1" : "_small"), nb, stream);
+  drain.armed = true;
+  if (raises_) GDV_HIP_RETURN_NOT_OK(hipMemsetAsync(base + err_off, 0, 8, stream));
+  if (by_value) {
+    GDV_RETURN_NOT_OK(rt.Launch(kernel, 1, plan_.opts.waves * 64, pin, stride, stream, kernel.function_small1));
+  } else {
+    GDV_HIP_RETURN_NOT_OK(hipMemcpyAsync(base, pin, stride * nb, hipMemcpyHostToDevice, stream));
+    GDV_RETURN_NOT_OK(rt.LaunchMany(kernel, 1, nb, plan_.opts.waves * 64, base, stream, /*small=*/true));
+  }
+  if (counts_device != nullptr)
+    GDV_HIP_RETURN_NOT_OK(hipMemcpyAsync(counts_device, base + cnt_off, 8 * static_cast<size_t>(nb), hipMemcpyDefault, stream));
+  const bool async = (flags & kEvalAsync) != 0 && !raises_ && counts_device != nullptr;
+  if (async) {
+    if (counts_host != nullptr)
+      for (int b = 0; b < nb; b++) counts_host[b] = -1;
+    block.release_after(stream);
+    lease.ReleaseAfter(stream);  // (nothing to give back when the block went by value)
+    drain.armed = false;
+    return Status::OK();
+  }
+  std::vector<int64_t> counts(nb, 0);
+  uint32_t err_bits = 0;
+  GDV_HIP_RETURN_NOT_OK(hipMemcpyAsync(counts.data(), base + cnt_off, 8 * static_cast<size_t>(nb), hipMemcpyDeviceToHost, stream));
+  if (raises_) GDV_HIP_RETURN_NOT_OK(hipMemcpyAsync(&err_bits, base + err_off, 4, hipMemcpyDeviceToHost, stream));
+  GDV_HIP_RETURN_NOT_OK(hipStreamSynchronize(stream));
+  drain.armed = false;
+  if (err_bits != 0) return Status::ExecutionError(ErrorMessage(err_bits));
+  if (counts_host != nullptr)
+    for (int b = 0; b < nb; b++) counts_host[b] = counts[b];
+  return Status::OK();
 }
 
 Status FilterProject::EvaluateChain(int64_t num_rows, const ColumnBuffers* cols, int num_cols, OutputBuffers* outs, int num_outs,

@@ -567,7 +567,7 @@ Status PlanFilter(const Schema& schema, const ExpressionPtr& condition,
 }
 
 Status PlanFilterProject(const Schema& schema, const ExpressionPtr& condition, const std::vector<ExpressionPtr>& exprs,
-                         SelectionMode index_mode, const CodegenOptions& opts, KernelPlan* plan) {
+                         SelectionMode index_mode, const CodegenOptions& opts, KernelPlan* plan, bool with_small) {
   if (!condition) return Status::Invalid("Condition cannot be null");
   if (exprs.empty()) return Status::Invalid("Expressions cannot be empty");
   GDV_RETURN_NOT_OK(ValidateExpression(schema, *condition));
@@ -596,6 +596,18 @@ Status PlanFilterProject(const Schema& schema, const ExpressionPtr& condition, c
     if (st.ok() && prefix) {
       *plan = std::move(windowed);
       plan->exact = direct;
+      // the small shape (one workgroup per batch) is the windowed body again: the same rule, with equality — text
+      // only here, compiled when a list of small batches first asks for it
+      if (with_small) {
+        auto small = std::make_shared<KernelPlan>();
+        st = PlanFilterProjectShape(schema, condition, exprs, index_mode, opts, FpShape::kSmall, small.get());
+        if (!st.ok() && st.code != kCodeGenError) return st;
+        if (st.ok() && small->literals == plan->literals && small->const_block == plan->const_block &&
+            small->input_fields == plan->input_fields && small->opts.subtiles == plan->opts.subtiles &&
+            small->opts.waves == plan->opts.waves && small->layout.total() == plan->layout.total() &&
+            small->fp_rounds == plan->fp_rounds && small->fp_window_rows == plan->fp_window_rows)
+          plan->small = small;
+      }
       return Status::OK();
     }
     if (!st.ok() && st.code != kCodeGenError) return st;

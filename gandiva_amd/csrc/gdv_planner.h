@@ -127,6 +127,10 @@ struct KernelPlan {
   // them turns out to be pure ASCII again.  Null when nothing consults the flag.
   std::shared_ptr<KernelPlan> exact;
   std::shared_ptr<KernelPlan> prepass;
+  // Fused filter-project: the SMALL shape of a windowed plan — one workgroup per batch, entries <name>_small(table) /
+  // <name>_small1(A), the windowed plan's argument block.  A kernel of its own, compiled when EvaluateMany first needs
+  // it; null for a plan that has the direct shape only.
+  std::shared_ptr<KernelPlan> small;
   std::vector<int> wave_segments;
   int fp_rounds = 1;  // fused filter-project: rounds of `subtiles` sub-tiles per wave tile (windowed shape: GDV_FP_K; direct: 1)
   int fp_window_rows = 0;  // fused filter-project, windowed shape: GDV_FP_CAP (0: the direct shape); `exact` = the direct shape
@@ -152,8 +156,9 @@ Status PlanFilter(const Schema& schema, const ExpressionPtr& condition,
 // output base by a decoupled look-back and stores the projections of the selected rows compacted
 // (+ the selection vector when index_mode != kNone).  plan->mode = index_mode.  CodeGenError for
 // plans the fused shape does not take (var-len columns or outputs): callers chain Filter + Projector.
+// with_small: also generate out->small for a windowed plan (tests compare the other shapes' text with and without it).
 Status PlanFilterProject(const Schema& schema, const ExpressionPtr& condition, const std::vector<ExpressionPtr>& exprs,
-                         SelectionMode index_mode, const CodegenOptions& opts, KernelPlan* out);
+                         SelectionMode index_mode, const CodegenOptions& opts, KernelPlan* out, bool with_small = true);
 
 Status ValidateExpression(const Schema& schema, const Expression& expr);
 

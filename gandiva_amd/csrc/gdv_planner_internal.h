@@ -300,7 +300,7 @@ Status AssembleStringsWave(CodeGen& cg, KernelPlan* plan, const std::vector<std:
                            const WordAccumulators& accs, const std::string& decls_before_loop,
                            const std::string& decls_in_pass, const std::string& after_row_loop,
                            const std::string& epilogue_after_loop, WaveKind kind, bool has_direct_pass);
-enum class FpShape { kDirect, kWindow };
+enum class FpShape { kDirect, kWindow, kSmall };  // kSmall: the windowed body, one workgroup per batch (many small batches)
 Status PlanFilterProjectShape(const Schema& schema, const ExpressionPtr& condition, const std::vector<ExpressionPtr>& exprs,
                               SelectionMode index_mode, const CodegenOptions& opts, FpShape shape, KernelPlan* plan);
 

@@ -135,7 +135,7 @@ const std::string& Runtime::arch() {
 
 static hipError_t LoadModule(const std::vector<char>& code, const std::string& name, CompiledKernel* k) {
   hipError_t e = hipModuleLoadData(&k->module, code.data());
-  if (e == hipSuccess) e = hipModuleGetFunction(&k->function, k->module, name.c_str());
+  if (e == hipSuccess && !k->small_only) e = hipModuleGetFunction(&k->function, k->module, name.c_str());
   return e;
 }
 
@@ -162,6 +162,8 @@ Status Runtime::GetKernel(const std::string& source, const std::string& kernel_n
   GDV_RETURN_NOT_OK(CompileToCodeObject(source, kernel_name, &code, &from_cache));
   auto k = std::make_unique<CompiledKernel>();
   k->name = kernel_name;
+  // (the small shape of a fused filter-project: a code object with the <name>_small / <name>_small1 entries alone)
+  k->small_only = source.find(" " + kernel_name + "(") == std::string::npos && source.find(kernel_name + "_small(") != std::string::npos;
   hipError_t le = LoadModule(code, kernel_name, k.get());
   if (le != hipSuccess && from_cache) {
     // a cached code object that does not load (truncated, built by another toolchain): drop

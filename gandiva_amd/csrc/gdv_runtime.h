@@ -34,6 +34,7 @@ struct CompiledKernel {
   hipFunction_t function_many = nullptr;  // <name>_many(const gdv_args* table), when the plan has one
   hipFunction_t function_small = nullptr; // <name>_small(const gdv_args* table): fused small-batch filter
   hipFunction_t function_small1 = nullptr;  // <name>_small1(const gdv_args A): the same for one batch, by value
+  bool small_only = false;  // the code object defines no <name>(A): `function` stays null (a fused filter-project's small shape)
   std::string name;
 };
 

@@ -1136,9 +1136,16 @@ class FilterProject:
         return _capi.take_string(_capi.lib().gdv_filter_project_dump_ir(self._h))
 
     def set_tuning(self, key, value):
-        """gdv_filter_project_set_tuning: "kernel" (-1 follow the selectivity / 0 windowed / 1 direct)."""
+        """gdv_filter_project_set_tuning: "kernel" (-1 follow the selectivity / 0 windowed / 1 direct), "small"
+        (0: evaluate_device_many goes batch by batch)."""
         if self._h is not None:
             _check(_capi.lib().gdv_filter_project_set_tuning(self._h, key.encode(), int(value)))
+
+    @property
+    def small_batch_rows(self):
+        """Rows one workgroup is given for one batch (0: the plan has no small shape): evaluate_device_many runs a list of
+        nb batches in one launch while none has more than nb times as many rows (at most 2^17)."""
+        return 0 if self._h is None else _capi.lib().gdv_filter_project_small_batch_rows(self._h)
 
     @property
     def kernel_shape(self):
@@ -1220,6 +1227,66 @@ class FilterProject:
             sel = SelectionVector(self._mode, indices, None if pending else count.value, device=True, count_tensor=cnt)
         self.last_count_tensor = cnt
         return outputs, sel
+
+    def evaluate_device_many(self, dbatches, outputs=None, indices=None, stream=None, sync=True):
+        """Many small HBM-resident batches in one launch (gdv_filter_project_evaluate_many): one
+        ``(DeviceColumns, SelectionVector or None)`` per batch, shaped like ``evaluate_device``'s result.
+        ``outputs`` / ``indices``: per batch, the buffers to write into (sized for the batch's rows).  sync=False
+        (plans that cannot raise): nothing waits, the counts stay on the device until someone asks.  A chain
+        (``fused`` is False) evaluates batch by batch."""
+        import torch
+        nb = len(dbatches)
+        if self._h is None:
+            return [self.evaluate_device(db, outputs=None if outputs is None else outputs[b],
+                                         indices=None if indices is None else indices[b], stream=stream, sync=sync)
+                    for b, db in enumerate(dbatches)]
+        lib = _capi.lib()
+        n_out = len(self._out_types)
+        tdt = {1: torch.int16, 2: torch.int32, 3: torch.int64}.get(self._mode)
+        batches = (_capi.gdv_filter_project_batch_t * max(nb, 1))()
+        keep, all_outs, all_idx = [], [], []
+        for b, db in enumerate(dbatches):
+            n = db.num_rows
+            cols = (gdv_column_t * max(len(db.columns), 1))(*[c._c() for c in db.columns])
+            vbytes = (n + 63) // 64 * 8
+            outs_b = None if outputs is None else outputs[b]
+            if outs_b is None:
+                outs_b = [DeviceColumn(t, n, torch.empty(_pad64(max(vbytes, 1)), dtype=torch.uint8, device="cuda"),
+                                       torch.empty(_pad64(max(vbytes if pa.types.is_boolean(t) else n * t.bit_width // 8, 1)),
+                                                   dtype=torch.uint8, device="cuda")) for t in self._out_types]
+            outs = (gdv_out_column_t * max(n_out, 1))()
+            for i, o in enumerate(outs_b):
+                outs[i].validity, outs[i].validity_size = o.validity.data_ptr(), o.validity.numel()
+                outs[i].data, outs[i].data_size = o.data.data_ptr(), o.data.numel()
+            idx = None if indices is None else indices[b]
+            if self._mode and idx is None:
+                idx = torch.empty(max(n, 1), dtype=tdt, device="cuda")
+            keep.append((cols, outs))
+            all_outs.append(outs_b)
+            all_idx.append(idx)
+            batches[b].num_rows, batches[b].cols, batches[b].num_cols = n, cols, len(db.columns)
+            batches[b].outs, batches[b].num_outs = outs, len(outs_b)
+            batches[b].out_indices = idx.data_ptr() if self._mode else None
+            batches[b].max_slots = idx.numel() if self._mode else 0
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        cnts = torch.zeros(max(nb, 1), dtype=torch.int64, device="cuda")
+        counts = (C.c_int64 * max(nb, 1))()
+        _check(lib.gdv_filter_project_evaluate_many(self._h, batches, nb, counts, C.c_void_p(cnts.data_ptr()),
+                                                    C.c_void_p(stream), 0 if sync else GDV_EVAL_ASYNC))
+        result = []
+        for b in range(nb):
+            pending = counts[b] < 0
+            cnt = cnts[b:b + 1]
+            for o in all_outs[b]:
+                o.length = dbatches[b].num_rows if pending else counts[b]
+                o.count_tensor = cnt if pending else None
+            sel = None
+            if self._mode:
+                sel = SelectionVector(self._mode, all_idx[b], None if pending else counts[b], device=True, count_tensor=cnt)
+            result.append((all_outs[b], sel))
+        self.last_count_tensor = cnts
+        return result
 
 
 def make_filter_project(schema, condition, children, index_dtype=None, configuration=None):

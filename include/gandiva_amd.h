@@ -384,8 +384,48 @@ char* gdv_filter_project_dump_ir(const gdv_filter_project_t* fp);
  * filter + selection-mode projector chain (round 4: ExecutionError); under GDV_EVAL_ASYNC *num_selected_device
  * then receives -1 — evaluate the batch with the synchronous call. */
 int gdv_filter_project_kernel_shape(const gdv_filter_project_t* fp);
-/* "kernel": -1 follow the selectivity (default), 0 / 1 pin the windowed / the direct kernel (tests, measurements). */
+/* "kernel": -1 follow the selectivity (default), 0 / 1 pin the windowed / the direct kernel (tests, measurements).
+ * "small": 0 / 1 (default 1): 0 makes gdv_filter_project_evaluate_many evaluate batch by batch.
+ * "small_rows": 0 .. 131072 (default 0 = the plan's own rule): the row cap of its one-launch path (measurements). */
 int gdv_filter_project_set_tuning(gdv_filter_project_t* fp, const char* key, int64_t value);
+/* Many small HBM-resident batches in ONE launch.  The look-back, the ticket and the memsets of
+ * gdv_filter_project_evaluate exist because a big batch spans many workgroups; a batch of a few thousand rows
+ * fits ONE.  Here every batch is filtered and projected by one workgroup that walks its workgroup tiles in row
+ * order and keeps the output base as a running total in LDS (the plan's third kernel, the SMALL shape: the
+ * windowed body without look-back; compiled on first use).  The workgroup zeroes the output bitmaps it ORs
+ * into itself, so the call enqueues one copy of the argument table and one kernel — with one batch the
+ * argument block travels by value and only the kernel is enqueued.  Device buffers only; outs[e] sized for num_rows rows as
+ * gdv_filter_project_evaluate asks (8-byte word granularity).  Buffers of a 0-row batch are not touched (its
+ * count is 0).  Results are those of gdv_filter_project_evaluate on each batch: data rows [0, count), validity
+ * / boolean words [0, ceil(count / 64)), indices and count.
+ * num_selected (host array, may be NULL with GDV_EVAL_ASYNC) / num_selected_device (int64[num_batches] in
+ * device or pinned memory, may be NULL) receive the counts.  With GDV_EVAL_ASYNC, a device array and a plan
+ * that cannot raise nothing waits and num_selected[b] = -1; plans that can raise wait, read the ONE error word
+ * the batches share and return GDV_EXECUTION_ERROR (which batch raised is not reported).
+ * The argument checks of the one-batch call are made for every batch before anything is enqueued; a failing
+ * one returns GDV_INVALID and names the batch ("batch 2: ...").
+ * Evaluated batch by batch on `stream` through gdv_filter_project_evaluate's path, with identical results: a
+ * list with a batch above the row cap (num_batches x gdv_filter_project_small_batch_rows, at most 2^17 rows), a plan whose rows are too wide for the LDS window (gdv_filter_project_kernel_shape = -1), more than
+ * 65535 batches, an argument table that does not fit half a pinned block, "small" = 0. */
+typedef struct {
+  int64_t num_rows;
+  const gdv_column_t* cols; /* one per schema field */
+  int num_cols;
+  gdv_out_column_t* outs;   /* one per expression, sized for num_rows rows */
+  int num_outs;
+  void* out_indices;        /* NULL with GDV_SEL_NONE */
+  int64_t max_slots;        /* >= num_rows when indices are emitted */
+} gdv_filter_project_batch_t;
+int gdv_filter_project_evaluate_many(const gdv_filter_project_t* fp, const gdv_filter_project_batch_t* batches,
+                                     int num_batches, int64_t* num_selected /* host, may be NULL with ASYNC */,
+                                     void* num_selected_device /* int64[num_batches], may be NULL */, void* stream,
+                                     uint32_t flags);
+/* Rows ONE workgroup is given for one batch of this plan: 512 KiB / the bytes a row moves (input values + outputs +
+ * index) — measured: up to there a single small batch through gdv_filter_project_evaluate_many beats
+ * gdv_filter_project_evaluate (profiles/filter_project_small_batches.txt).  The workgroups of a list run side by side, so
+ * a list of num_batches batches takes the one-launch path up to num_batches times as many rows per batch, at most 2^17.
+ * 0: the plan has no small shape. */
+int64_t gdv_filter_project_small_batch_rows(const gdv_filter_project_t* fp);
 void gdv_filter_project_free(gdv_filter_project_t* fp);
 
 /* ---- One call, all the GPUs of a node (round 6) -------------------------
@@ -678,6 +718,13 @@ int gdv_precompile_projector(const gdv_schema_t* schema, gdv_expression_t* const
 int gdv_precompile_filter(const gdv_schema_t* schema, gdv_expression_t* condition);
 int gdv_precompile_filter_project(const gdv_schema_t* schema, gdv_expression_t* condition, gdv_expression_t* const* exprs,
                                   int num_exprs, int index_mode);
+/* The kernel text of ONE shape of a fused plan, without a device (tests, tools): shape 0 = the main kernel (the windowed
+ * one where the plan has that shape), 1 = the direct kernel behind a windowed one, 2 = the small kernel of
+ * gdv_filter_project_evaluate_many.  request_small = 0 plans without the small shape (shapes 0 and 1 must not differ for
+ * it); compile != 0 also compiles that text to a gfx950 code object.  NULL when the plan has no such shape
+ * (GDV_CODE_GEN_ERROR in gdv_last_error) or on failure.  Free with gdv_free_string. */
+char* gdv_filter_project_plan_text(const gdv_schema_t* schema, gdv_expression_t* condition, gdv_expression_t* const* exprs,
+                                   int num_exprs, int index_mode, int shape, int request_small, int compile);
 /* Pattern compilers of the planner, callable on their own (no device): a caller can check a regexp_like / regexp_matches
  * pattern, or a to_date pattern, before building an expression around it; tests drive the device functions' host build with
  * the tables.  gdv_compile_regex: `table` receives GDV_REGEX_TABLE_BYTES bytes (flags, nullable, predicates[8], first[8], last[8],

@@ -25,7 +25,10 @@ def plan_source(which):
         sh = gg._make_schema(W.c3_schema())
         cond, ex = W.c3_condition(), W.c3_sum_expression()
         arr = (C.c_void_p * len(ex))(*[e._h for e in ex])
-        rc = lib.gdv_precompile_filter_project(sh, cond._h, arr, len(ex), int(os.environ.get("FP_MODE", "2")))
+        mode = int(os.environ.get("FP_MODE", "2"))
+        rc = lib.gdv_precompile_filter_project(sh, cond._h, arr, len(ex), mode)
+        # ... and its small shape (gdv_filter_project_evaluate_many), which no Make compiles
+        lib.gdv_free_string(lib.gdv_filter_project_plan_text(sh, cond._h, arr, len(ex), mode, 2, 1, 1))
     elif which == "c3":
         sh = gg._make_schema(W.c3_schema())
         cond = W.c3_condition()

@@ -7,6 +7,7 @@
 // and the filter (a > k1 AND b < k2 over int64): sync vs gdv_filter_evaluate_async.
 // Prints microseconds per batch.   g++ -O2 -std=c++17 tools/small_batch_bench.cc -Iinclude
 //   -Lgandiva_amd -lgandiva_amd -Wl,-rpath,$PWD/gandiva_amd -o tools/small_batch_bench
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -22,7 +23,13 @@ static double Now() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-int main() {
+static void FilterProjectSection();
+
+int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "fp") == 0) {  // the fused filter-project section alone
+    FilterProjectSection();
+    return 0;
+  }
   const gdv_type_t f64 = {GDV_TYPE_DOUBLE, 0, 0}, i64 = {GDV_TYPE_INT64, 0, 0}, boolean = {GDV_TYPE_BOOL, 0, 0};
   gdv_schema_t* schema = gdv_schema_new();
   const char* names[4] = {"a", "b", "c", "d"};
@@ -195,5 +202,185 @@ int main() {
     }
     gdv_device_free(idx); gdv_device_free(cnt);
   }
+  FilterProjectSection();
   return 0;
+}
+
+// ---------------------------------------------------------------- fused filter -> project over small batches
+// 256 HBM-resident batches per round, every batch with inputs and outputs of its own; microseconds per batch, the MEDIAN
+// of five rounds behind a warm-up round.  Two plans at ~12 % and ~100 % selected:
+//   k2f        a > k1 AND b < k2, a + b projected, uint32 indices (the K2F workload's plan)
+//   threshold  a > t; a + b, x * x, (a < b) OR f, if (b != 0) a / b else -1, k + 7; uint32 indices (tests/test_filter_project.py)
+//   (a) sync   gdv_filter_project_evaluate, one batch per call, the call waits
+//   (b) async  the same with GDV_EVAL_ASYNC and a device count word, one wait per round (a plan that can raise waits anyway)
+//   (c) many   gdv_filter_project_evaluate_many over the 256 batches (one launch up to the plan's row cap)
+//   (d) many1  gdv_filter_project_evaluate_many with one batch per call (the by-value entry)
+//   (d*) / (c*)  (d) and (c) with the row cap lifted to 2^17 ("small_rows"): what one workgroup costs beyond the cap
+//   filter     gdv_filter_evaluate_many on the predicate alone over the 256 batches (the neighbour figure)
+namespace {
+
+struct FpPlan {
+  const char* name;
+  gdv_schema_t* schema;
+  int num_cols;
+  gdv_filter_project_t* fp[2];  // ~12 %, ~100 %
+  gdv_filter_t* flt[2];
+  int num_outs;
+  int out_width[5];             // bytes per row; 0 = a bitmap
+};
+
+template <typename F>
+double MedianRound(int nb, F&& round) {
+  round();
+  CHECK(gdv_device_synchronize() == GDV_OK);
+  std::vector<double> t;
+  for (int rep = 0; rep < 5; rep++) {
+    const double t0 = Now();
+    round();
+    CHECK(gdv_device_synchronize() == GDV_OK);
+    t.push_back(Now() - t0);
+  }
+  std::sort(t.begin(), t.end());
+  return t[2] / nb * 1e6;
+}
+
+}  // namespace
+
+static void FilterProjectSection() {
+  const gdv_type_t i64 = {GDV_TYPE_INT64, 0, 0}, f64 = {GDV_TYPE_DOUBLE, 0, 0}, i32 = {GDV_TYPE_INT32, 0, 0}, boolean = {GDV_TYPE_BOOL, 0, 0};
+  auto fn2 = [](const char* name, gdv_node_t* x, gdv_node_t* y, gdv_type_t t) {
+    gdv_node_t* args[2] = {x, y};
+    return gdv_node_function(name, args, 2, t);
+  };
+  auto lit64 = [&](int64_t v) { return gdv_node_literal(i64, &v, 0); };
+  FpPlan plans[2];
+  {  // k2f
+    FpPlan& p = plans[0];
+    p = FpPlan{"k2f", gdv_schema_new(), 2, {nullptr, nullptr}, {nullptr, nullptr}, 1, {8, 0, 0, 0, 0}};
+    CHECK(gdv_schema_add_field(p.schema, "a", i64, 1) == GDV_OK);
+    CHECK(gdv_schema_add_field(p.schema, "b", i64, 1) == GDV_OK);
+    const int64_t k1[2] = {499, -1}, k2[2] = {250, 1000000};
+    for (int s = 0; s < 2; s++) {
+      auto cond = [&] {
+        gdv_node_t* conj[2] = {fn2("greater_than", gdv_node_field("a", i64), lit64(k1[s]), boolean),
+                               fn2("less_than", gdv_node_field("b", i64), lit64(k2[s]), boolean)};
+        return gdv_condition_new(gdv_node_and(conj, 2));
+      };
+      gdv_expression_t* ex[1] = {gdv_expression_new(fn2("add", gdv_node_field("a", i64), gdv_node_field("b", i64), i64), "s", i64)};
+      CHECK(gdv_filter_project_make(p.schema, cond(), ex, 1, GDV_SEL_UINT32, nullptr, &p.fp[s]) == GDV_OK);
+      CHECK(gdv_filter_make(p.schema, cond(), nullptr, &p.flt[s]) == GDV_OK);
+    }
+  }
+  {  // threshold
+    FpPlan& p = plans[1];
+    p = FpPlan{"threshold", gdv_schema_new(), 5, {nullptr, nullptr}, {nullptr, nullptr}, 5, {8, 8, 0, 8, 4}};
+    CHECK(gdv_schema_add_field(p.schema, "a", i64, 1) == GDV_OK);
+    CHECK(gdv_schema_add_field(p.schema, "b", i64, 1) == GDV_OK);
+    CHECK(gdv_schema_add_field(p.schema, "x", f64, 1) == GDV_OK);
+    CHECK(gdv_schema_add_field(p.schema, "k", i32, 1) == GDV_OK);
+    CHECK(gdv_schema_add_field(p.schema, "f", boolean, 1) == GDV_OK);
+    const int64_t thr[2] = {879, -1};
+    for (int s = 0; s < 2; s++) {
+      auto A = [&] { return gdv_node_field("a", i64); };
+      auto B = [&] { return gdv_node_field("b", i64); };
+      auto cond = [&] { return gdv_condition_new(fn2("greater_than", A(), lit64(thr[s]), boolean)); };
+      gdv_node_t* either[2] = {fn2("less_than", A(), B(), boolean), gdv_node_field("f", boolean)};
+      const int32_t seven = 7;
+      gdv_expression_t* ex[5] = {
+          gdv_expression_new(fn2("add", A(), B(), i64), "s", i64),
+          gdv_expression_new(fn2("multiply", gdv_node_field("x", f64), gdv_node_field("x", f64), f64), "xx", f64),
+          gdv_expression_new(gdv_node_or(either, 2), "lt_or_f", boolean),
+          gdv_expression_new(gdv_node_if(fn2("not_equal", B(), lit64(0), boolean), fn2("divide", A(), B(), i64), lit64(-1), i64), "q", i64),
+          gdv_expression_new(fn2("add", gdv_node_field("k", i32), gdv_node_literal(i32, &seven, 0), i32), "k7", i32)};
+      CHECK(gdv_filter_project_make(p.schema, cond(), ex, 5, GDV_SEL_UINT32, nullptr, &p.fp[s]) == GDV_OK);
+      CHECK(gdv_filter_make(p.schema, cond(), nullptr, &p.flt[s]) == GDV_OK);
+    }
+  }
+  const int NB = 256;
+  printf("\nfused filter-project, %d batches per round, microseconds per batch (median of 5 rounds); cap = rows per batch of the one-launch path\n", NB);
+  printf("%10s %5s %8s %8s %9s %9s %9s %9s %9s %9s %9s\n", "plan", "sel", "rows", "cap", "(a) sync", "(b) async", "(c) many", "(d) many1",
+         "(d*)", "(c*)", "filter");
+  for (int64_t rows : {1024, 4096, 16384, 65536}) {
+    const int64_t vbytes = ((rows + 63) / 64) * 8;
+    std::vector<int64_t> ha(rows), hb_k2f(rows), hb_thr(rows);
+    std::vector<double> hx(rows);
+    std::vector<int32_t> hk(rows);
+    std::vector<uint8_t> ones(vbytes, 0xFF), hf(vbytes);
+    uint64_t state = 88172645463325252ull;
+    auto next = [&] { state ^= state << 13; state ^= state >> 7; state ^= state << 17; return state; };
+    for (int64_t i = 0; i < rows; i++) {
+      ha[i] = (int64_t)(next() % 1000); hb_k2f[i] = (int64_t)(next() % 1000); hb_thr[i] = (int64_t)(next() % 8);
+      hx[i] = (double)(next() % 4096) * 0.5; hk[i] = (int32_t)(next() % 100000);
+    }
+    for (auto& byte : hf) byte = (uint8_t)next();
+    for (FpPlan& p : plans) {
+      // NB batches with inputs, outputs, indices of their own
+      std::vector<void*> owned;
+      auto dev = [&](int64_t bytes, const void* src) {
+        void* d = nullptr;
+        CHECK(gdv_device_alloc(bytes, &d) == GDV_OK);
+        if (src != nullptr) CHECK(gdv_memcpy_h2d(d, src, bytes) == GDV_OK);
+        owned.push_back(d);
+        return d;
+      };
+      std::vector<std::vector<gdv_column_t>> cols(NB, std::vector<gdv_column_t>(p.num_cols));
+      std::vector<std::vector<gdv_out_column_t>> outs(NB, std::vector<gdv_out_column_t>(p.num_outs));
+      std::vector<gdv_filter_project_batch_t> fpb(NB);
+      std::vector<gdv_filter_batch_t> fb(NB);
+      void* counts_dev = dev(8 * NB, nullptr);
+      for (int b = 0; b < NB; b++) {
+        const void* src[5] = {ha.data(), p.num_cols == 2 ? (const void*)hb_k2f.data() : (const void*)hb_thr.data(), hx.data(), hk.data(), hf.data()};
+        const int64_t bytes[5] = {rows * 8, rows * 8, rows * 8, rows * 4, vbytes};
+        for (int k = 0; k < p.num_cols; k++) {
+          memset(&cols[b][k], 0, sizeof(gdv_column_t));
+          cols[b][k].validity = dev(vbytes, ones.data()); cols[b][k].validity_size = vbytes;
+          cols[b][k].data = dev(bytes[k], src[k]); cols[b][k].data_size = bytes[k];
+        }
+        for (int e = 0; e < p.num_outs; e++) {
+          memset(&outs[b][e], 0, sizeof(gdv_out_column_t));
+          const int64_t dbytes = p.out_width[e] == 0 ? vbytes : rows * p.out_width[e];
+          outs[b][e].validity = dev(vbytes, nullptr); outs[b][e].validity_size = vbytes;
+          outs[b][e].data = dev(dbytes, nullptr); outs[b][e].data_size = dbytes;
+        }
+        void* idx = dev(rows * 4, nullptr);
+        fpb[b] = gdv_filter_project_batch_t{rows, cols[b].data(), p.num_cols, outs[b].data(), p.num_outs, idx, rows};
+        fb[b] = gdv_filter_batch_t{rows, cols[b].data(), p.num_cols, idx, rows};
+      }
+      std::vector<int64_t> counts(NB);
+      for (int s = 0; s < 2; s++) {
+        gdv_filter_project_t* fp = p.fp[s];
+        const double t_sync = MedianRound(NB, [&] {
+          for (int b = 0; b < NB; b++)
+            CHECK(gdv_filter_project_evaluate(fp, rows, fpb[b].cols, p.num_cols, fpb[b].outs, p.num_outs, fpb[b].out_indices, rows, &counts[b],
+                                              nullptr, GDV_MEM_DEVICE, nullptr, 0) == GDV_OK);
+        });
+        const int64_t want0 = counts[0];
+        const double t_async = MedianRound(NB, [&] {
+          for (int b = 0; b < NB; b++)
+            CHECK(gdv_filter_project_evaluate(fp, rows, fpb[b].cols, p.num_cols, fpb[b].outs, p.num_outs, fpb[b].out_indices, rows, &counts[b],
+                                              (char*)counts_dev + 8 * b, GDV_MEM_DEVICE, nullptr, GDV_EVAL_ASYNC) == GDV_OK);
+        });
+        auto many = [&] { CHECK(gdv_filter_project_evaluate_many(fp, fpb.data(), NB, counts.data(), nullptr, nullptr, 0) == GDV_OK); };
+        auto many1 = [&] {
+          for (int b = 0; b < NB; b++) CHECK(gdv_filter_project_evaluate_many(fp, &fpb[b], 1, &counts[b], nullptr, nullptr, 0) == GDV_OK);
+        };
+        const long long cap = (long long)gdv_filter_project_small_batch_rows(fp);
+        const double t_many = MedianRound(NB, many);
+        if (counts[0] != want0 || counts[NB - 1] != want0) { fprintf(stderr, "evaluate_many: count %lld, one batch %lld\n", (long long)counts[0], (long long)want0); exit(1); }
+        const double t_many1 = MedianRound(NB, many1);
+        CHECK(gdv_filter_project_set_tuning(fp, "small_rows", 131072) == GDV_OK);
+        const double t_many1_lifted = MedianRound(NB, many1);
+        const double t_many_lifted = MedianRound(NB, many);
+        if (counts[0] != want0 || counts[NB - 1] != want0) { fprintf(stderr, "evaluate_many (cap lifted): count %lld, one batch %lld\n", (long long)counts[0], (long long)want0); exit(1); }
+        CHECK(gdv_filter_project_set_tuning(fp, "small_rows", 0) == GDV_OK);
+        const double t_filter = MedianRound(NB, [&] {
+          CHECK(gdv_filter_evaluate_many(p.flt[s], fb.data(), NB, GDV_SEL_UINT32, counts.data(), nullptr, nullptr, 0) == GDV_OK);
+        });
+        printf("%10s %4.0f%% %8lld %8lld %9.1f %9.1f %9.1f %9.1f %9.1f %9.1f %9.1f\n", p.name, 100.0 * (double)want0 / (double)rows, (long long)rows,
+               cap, t_sync, t_async, t_many, t_many1, t_many1_lifted, t_many_lifted, t_filter);
+        fflush(stdout);
+      }
+      for (void* d : owned) gdv_device_free(d);
+    }
+  }
 }
