@@ -1257,14 +1257,31 @@ GDV_DEV gdv_int128 truncate_decimal128(gdv_int128 x, int xp, int xs, int op, int
 GDV_DEV gdv_int128 truncate_decimal128_int32(gdv_int128 x, int xp, int xs, gdv_int32 k, int op, int os) { return gdv_dec_round_to(x, xs, k, 1, op, os); }
 GDV_DEV gdv_int128 ceil_decimal128(gdv_int128 x, int xp, int xs, int op, int os) { return gdv_dec_round_to(x, xs, 0, 2, op, os); }
 GDV_DEV gdv_int128 floor_decimal128(gdv_int128 x, int xp, int xs, int op, int os) { return gdv_dec_round_to(x, xs, 0, 3, op, os); }
+// the double nearest to a 128-bit magnitude, ties to even, rounded ONCE: below 2^64 the conversion of the uint64 is that;
+// above, the top 64 significant bits are kept, every bit shifted out is ORed into the lowest one (it lies ten places
+// below the rounding position, so it can only break a tie, never make one) and the exact power of two is multiplied back
+GDV_DEV gdv_float64 gdv_u128_to_f64(gdv_uint128 mag) {
+  gdv_uint64 h = (gdv_uint64)(mag >> 64);
+  if (h == 0) return (gdv_float64)(gdv_uint64)mag;
+  int sh = 1;  // the bit length of the high word
+  gdv_float64 two_sh = 2.0;
+  if (h >> 32) { h >>= 32; sh += 32; two_sh *= 4294967296.0; }
+  if (h >> 16) { h >>= 16; sh += 16; two_sh *= 65536.0; }
+  if (h >> 8) { h >>= 8; sh += 8; two_sh *= 256.0; }
+  if (h >> 4) { h >>= 4; sh += 4; two_sh *= 16.0; }
+  if (h >> 2) { h >>= 2; sh += 2; two_sh *= 4.0; }
+  if (h >> 1) { sh += 1; two_sh *= 2.0; }
+  const gdv_uint64 top = (gdv_uint64)(mag >> sh);
+  const gdv_uint64 sticky = (mag & (((gdv_uint128)1 << sh) - 1)) != 0 ? 1ull : 0ull;
+  return (gdv_float64)(top | sticky) * two_sh;
+}
 GDV_DEV gdv_float64 castFLOAT8_decimal128(gdv_int128 x, int xp, int xs, int op, int os) {
-  // two correctly rounded steps: int128 -> double, then divide by the exact power of ten
-  // (10^k is exact in binary64 for k <= 22; larger scales lose at most 1 ulp more)
+  // two correctly rounded steps: int128 -> the nearest double, then one division by p, where p is 1.0 multiplied by 10.0
+  // `xs` times (exactly 10^xs up to xs = 22; beyond, p itself carries the rounding of those multiplications)
   gdv_float64 p = 1.0;
   for (int i = 0; i < xs; i++) p *= 10.0;
   const gdv_uint128 mag = x < 0 ? (gdv_uint128)(-x) : (gdv_uint128)x;
-  const gdv_float64 m = (gdv_float64)(gdv_uint64)(mag >> 64) * 18446744073709551616.0 +
-                        (gdv_float64)(gdv_uint64)mag;
+  const gdv_float64 m = gdv_u128_to_f64(mag);
   return (x < 0 ? -m : m) / p;
 }
 GDV_DEV gdv_int64 castBIGINT_decimal128(gdv_int128 x, int xp, int xs, int op, int os) {

@@ -927,9 +927,10 @@ static int u256_div10(u256* v) { /* returns the removed digit */
   return (int)rem;
 }
 static void u256_inc(u256* v) { for (int i = 0; i < 4; i++) if (++v->w[i] != 0) break; }
-static void u256_mul10(u256* v) {
+static int u256_mul10(u256* v) { /* returns what left the 256 bits (0: nothing) */
   u128 carry = 0;
   for (int i = 0; i < 4; i++) { u128 cur = (u128)v->w[i] * 10 + carry; v->w[i] = (uint64_t)cur; carry = cur >> 64; }
+  return (int)carry;
 }
 static int u256_cmp(const u256* a, const u256* b) {
   for (int i = 3; i >= 0; i--) if (a->w[i] != b->w[i]) return a->w[i] < b->w[i] ? -1 : 1;
@@ -999,7 +1000,9 @@ static void u256_divmod(const u256* num, const u256* den, u256* q, u256* r) {
 }
 static i128 dec_div(i128 x, int xs, i128 y, int ys, int os) {
   u256 num = u256_from(mag128(x)), den = u256_from(mag128(y)), q, r;
-  for (int k = 0; k < os - xs + ys; k++) u256_mul10(&num);
+  /* |x| * 10^(os - xs + ys) can leave 256 bits (dec(38,0) / dec(38,37): 43 digits are appended); the quotient by a divisor
+   * below 10^38 then has more than 38 digits: overflow -> 0 */
+  for (int k = 0; k < os - xs + ys; k++) if (u256_mul10(&num)) return 0;
   u256_divmod(&num, &den, &q, &r);
   /* round half away from zero: 2 * r >= den */
   u256 twice = r;
@@ -1025,9 +1028,11 @@ static int dec_cmp(i128 x, int xs, i128 y, int ys) {
   return xn ? -c : c;
 }
 static i128 dec_rescale(i128 x, int xs, int op, int os) {
-  i128 r;
-  if (os >= xs) r = x * pow10_128(os - xs);
-  else { r = dec_finish(u256_from(mag128(x)), x < 0, xs - os); }
+  /* scaling up happens in 256 bits (|x| <= 10^38 and at most 38 digits are appended): a 128-bit product would wrap before
+   * the precision check sees it */
+  u256 m = u256_from(mag128(x));
+  for (int k = xs; k < os; k++) u256_mul10(&m);
+  i128 r = dec_finish(m, x < 0, xs > os ? xs - os : 0);
   i128 lim = pow10_128(op);
   return (r >= lim || r <= -lim) ? 0 : r;
 }
@@ -1596,14 +1601,21 @@ static void eval_function(const node* n, ctx* c, int64_t row0, int cnt, const ui
       else if ((op = cmp_op(f)) >= 0) { int cc = dec_cmp(x, xs, y, ys); out->v[i].i = CMP(op, cc, 0); }
       else if (!strcmp(f, "negative")) out->v[i].q = -x;
       else if (!strcmp(f, "abs")) out->v[i].q = x < 0 ? -x : x;
+      else if (!strcmp(f, "greatest")) out->v[i].q = dec_cmp(x, xs, y, ys) >= 0 ? x : y;   /* one decimal type on both sides */
+      else if (!strcmp(f, "least")) out->v[i].q = dec_cmp(x, xs, y, ys) <= 0 ? x : y;
       else if (!strcmp(f, "castDECIMAL")) {
         if (t0 == T_DEC) out->v[i].q = dec_rescale(x, xs, n->prec, n->scale);
         else out->v[i].q = dec_rescale((i128)a[0].v[i].i, 0, n->prec, n->scale);
       } else if (!strcmp(f, "castFLOAT8")) {
         double p10 = 1.0;
         for (int k = 0; k < xs; k++) p10 *= 10.0;
+        /* the magnitude -> the nearest double in ONE rounding: halved until it fits 64 bits, every bit that falls off
+         * kept as a sticky lowest bit, then the halvings multiplied back (exact) */
         u128 m = mag128(x);
-        double md = (double)(uint64_t)(m >> 64) * 18446744073709551616.0 + (double)(uint64_t)m;
+        double back = 1.0;
+        int lost = 0;
+        while (m >> 64) { lost |= (int)(m & 1); m >>= 1; back *= 2.0; }
+        double md = (double)((uint64_t)m | (uint64_t)lost) * back;
         out->v[i].d = (x < 0 ? -md : md) / p10;
       } else if (!strcmp(f, "castBIGINT")) out->v[i].i = (int64_t)dec_finish(u256_from(mag128(x)), x < 0, xs);
       else if (!strcmp(f, "isnull")) { out->v[i].i = !a[0].valid[i]; out->valid[i] = 1; }

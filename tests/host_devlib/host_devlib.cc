@@ -77,6 +77,18 @@ int host_decimal_to_int64(const void* xv, int xp, int xs, long long* out, long n
   for (long i = 0; i < n; i++) out[i] = castBIGINT_decimal128(x[i], xp, xs, 0, 0);
   return 0;
 }
+// op: 0 castFLOAT8 (out: double), 1 abs, 2 negative (out: 16-byte values)
+int host_decimal_unary(int op, const void* xv, int xp, int xs, void* out, long n) {
+  const gdv_int128* x = static_cast<const gdv_int128*>(xv);
+  for (long i = 0; i < n; i++) {
+    switch (op) {
+      case 0: static_cast<gdv_float64*>(out)[i] = castFLOAT8_decimal128(x[i], xp, xs, 0, 0); break;
+      case 1: static_cast<gdv_int128*>(out)[i] = abs_decimal128(x[i], xp, xs, xp, xs); break;
+      default: static_cast<gdv_int128*>(out)[i] = negative_decimal128(x[i], xp, xs, xp, xs); break;
+    }
+  }
+  return 0;
+}
 int host_decimal_compare(const void* xv, int xp, int xs, const void* yv, int yp, int ys, signed char* out, long n) {
   const gdv_int128* x = static_cast<const gdv_int128*>(xv);
   const gdv_int128* y = static_cast<const gdv_int128*>(yv);

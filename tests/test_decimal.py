@@ -241,6 +241,12 @@ def test_hip_decimal_ops_match_oracle(case):
     got = gandiva.make_projector(batch.schema, exprs, None).evaluate(batch)
     for g, w, e in zip(got, oracle.project(exprs, batch), exprs):
         assert_bit_exact(g, w, str(e))
+    # castFLOAT8 also against its rule, which the oracle and the kernel once missed together: the unscaled integer -> the
+    # nearest double (CPython's float(int) rounds once), then one division by 1.0 multiplied by 10.0 `scale` times
+    p = 1.0
+    for _ in range(ta.scale):
+        p *= 10.0
+    assert got[9].to_pylist() == [None if v is None else float(int(v.scaleb(ta.scale, CTX))) / p for v in a.to_pylist()]
 
 
 @pytest.mark.gpu
